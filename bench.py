@@ -9,7 +9,11 @@ Infinity Cache).  With --gpus N (torch.distributed.run, one rank per GPU)
 every rank runs its own independent stream (weak scaling, no collective on
 the data path; only the barrier and the max-over-ranks of the timed region).
 
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
+A plain run sets up, warms up, times the steps and prints ONE JSON line
+(rank 0).  --full adds the side measurements to that line (the pyramid-only
+stage, the live HBM probe, the PMC traffic of the committed profiles, the
+CPU baseline); --dump-outputs DIR writes a seeded sample of the chunk layers
+the last timed step produced.  See DESIGN.md "Measurement".
 """
 import argparse
 import ctypes as C
@@ -141,6 +145,46 @@ def fill_ring(torch, ring, dtype, seed):
         ring.view(torch.uint8).random_(0, 256, generator=g)
     else:
         ring.view(torch.float32).uniform_(0.0, 65535.0, generator=g)
+
+
+DUMP_VALUES = 8 << 20  # --dump-outputs: float32 values over all levels (32 MiB)
+DUMP_SEED = 20240
+
+
+def dump_outputs(st, cfg, out_dir, fw_before, fw_after, pyramid_only=False):
+    """--dump-outputs: what the last timed step left for its caller, as
+    aqz_stage_copy_layer hands it over: of every level, the chunk layers that
+    step completed (frames fw_before[l]..fw_after[l]) and their has_data
+    flags.  Written as float32 (exact for u8 / u16 / f32 pixels):
+    level<l>.npy holds, layer after layer, the pixels of each layer at a
+    fixed seeded sample of positions (the whole layer when it is small; the
+    positions depend only on the level, the layer's place in the step and the
+    layer's size); level<l>_has_data.npy the flags of those layers."""
+    npdt = {U8: np.uint8, U16: np.uint16, F32: np.float32}[cfg["dtype"]]
+    os.makedirs(out_dir, exist_ok=True)
+    # (a pyramid-only stage keeps no level-0 layers)
+    levels = [l for l in range(1 if pyramid_only else 0, st.n_levels())
+              if fw_after[l] > fw_before[l]]
+    for l in levels:
+        lay = st.layout(l)
+        F, slots = lay["frames_per_layer"], lay["layer_slots"]
+        # complete layers the step wrote into, still in the ring
+        first = max(fw_before[l] // F, (fw_after[l] - 1) // F - slots + 1, 0)
+        layers = range(first, fw_after[l] // F)
+        share = DUMP_VALUES // len(levels) // max(1, len(layers))
+        px, has = [], []
+        for i, layer in enumerate(layers):
+            buf, flags = st.copy_layer(l, layer)
+            v = buf.view(npdt)
+            if v.size > share:
+                rng = np.random.default_rng([DUMP_SEED, l, i, v.size])
+                v = v[np.sort(rng.integers(0, v.size, size=share))]
+            px.append(v.astype(np.float32))
+            has.append(flags.astype(np.float32))
+        empty = np.empty(0, np.float32)
+        np.save(os.path.join(out_dir, f"level{l}.npy"), np.concatenate(px) if px else empty)
+        np.save(os.path.join(out_dir, f"level{l}_has_data.npy"),
+                np.concatenate(has) if has else empty)
 
 
 def device_code_sha256(path):
@@ -622,12 +666,22 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements and add "
+                         "them to the line: the pyramid-only stage, the live HBM probe, "
+                         "roofline.traffic from the committed PMC summaries, the CPU "
+                         "baseline (each has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a seeded sample of "
+                         "every level's chunk layers, and their has_data flags) as "
+                         "float32 DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--pyramid-only", action="store_true",
                     help="skip the level-0 tile split (downsample levels only)")
     ap.add_argument("--no-pyramid-only-line", action="store_true",
-                    help="do not add the pyramid-only side measurement")
+                    help="--full: do not add the pyramid-only side measurement")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="diagnostic: roofline.achieved from the wall time per launch "
                          "instead of the HIP events bracketing the timed region")
@@ -664,7 +718,7 @@ def main():
                     help="XY-transposed storage order (storage_dimension_order swaps the "
                          "last two dims; the frames stay in acquisition order)")
     ap.add_argument("--no-hbm-probe", action="store_true",
-                    help="skip the live streaming probe of this device's HBM rates")
+                    help="--full: skip the live streaming probe of this device's HBM rates")
     ap.add_argument("--placement-tries", type=int, default=PLACEMENT["placement_tries"],
                     help="aqz_stage_options.placement_tries of the device-resident stages "
                          "(0: keep the first allocation)")
@@ -679,6 +733,9 @@ def main():
 
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.dump_outputs and (args.e2e or args.gpus > 1):
+        sys.exit("--dump-outputs writes the device-resident run of one GPU "
+                 "(no --e2e, --gpus 1)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # No launcher: start one rank per GPU ourselves, before this process
         # has touched the GPU, and exit with the launcher's status.
@@ -730,9 +787,10 @@ def main():
         planes = [lv[1][1] for lv in aqz.pyramid_levels(cfg["dims"])]
         slab = z_slab(planes[0], world, rank, 1 << z_levels(planes))
 
-    def run(pyramid_only, steps, warmup):
+    def run(pyramid_only, steps, warmup, dump_dir=None):
         """Time `steps` launches of B frames (after `warmup`) between
-        barrier + device sync on both sides; max over ranks."""
+        barrier + device sync on both sides; max over ranks.  dump_dir: write
+        the last launch's chunk layers there afterwards (dump_outputs)."""
         kw = dict(force_levels=cfg["force_levels"], max_batch_frames=B,
                   layer_slots=layer_slots_for(cfg, B),
                   skip_level0_split=pyramid_only, placement_tries=args.placement_tries)
@@ -807,6 +865,12 @@ def main():
             emitted = [steps * B * planes[l] // planes[0] for l in range(len(sizes))]
         else:
             emitted = [st.frames_written(l) - fw0[l] for l in range(len(sizes))]
+        if dump_dir and steps > 0:
+            # every launch writes the same number of frames to a level
+            fw1 = [st.frames_written(l) for l in range(len(sizes))]
+            dump_outputs(st, cfg, dump_dir,
+                         [b - (b - a) // steps for a, b in zip(fw0, fw1)], fw1,
+                         pyramid_only)
         st.close()
         del ring
         out_bytes = sum(n * h * w * bpp for n, (h, w) in zip(emitted[1:], sizes[1:]))
@@ -830,7 +894,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    main_run = run(args.pyramid_only, args.steps, args.warmup)
+    main_run = run(args.pyramid_only, args.steps, args.warmup, args.dump_outputs)
     per_rank = None
     if dist:
         # every rank's own kernel time, placement and creation cost, gathered
@@ -850,11 +914,12 @@ def main():
                 "stage_create_s": mp.get("stage_create_s")}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
+    # the side measurements take runs of their own: --full only
     side = None
-    if not args.pyramid_only and not args.no_pyramid_only_line:
+    if args.full and not args.pyramid_only and not args.no_pyramid_only_line:
         side = run(True, max(5, args.steps // 2), 2)
     probe = None
-    if not args.no_hbm_probe:
+    if args.full and not args.no_hbm_probe:
         probe = hbm_probe(aqz, dev.index)
     sizes, elapsed, value = main_run["sizes"], main_run["elapsed"], main_run["value"]
     kernel, avg_ms, achieved = main_run["kernel"], main_run["avg_ms"], main_run["achieved"]
@@ -863,9 +928,11 @@ def main():
     pl["placement_tries"] = args.placement_tries
     # how the chunk-layer rings were allocated (aqz_placement_report.mode)
     pl["ring_allocation"] = ring_allocation(pl)
-    traffic, traffic_src, prof = pmc_traffic(args.config, args.pyramid_only, kernel, B,
-                                             pl["ring_allocation"], avg_ms, lib_sha256(),
-                                             lib_device_code_sha256())
+    traffic, traffic_src, prof = None, None, None
+    if args.full:
+        traffic, traffic_src, prof = pmc_traffic(args.config, args.pyramid_only, kernel, B,
+                                                 pl["ring_allocation"], avg_ms, lib_sha256(),
+                                                 lib_device_code_sha256())
 
     result = {
         "metric": f"input GB/s, device-resident multiscale downsample, {DTYPE_WORDS[dt]} "
@@ -985,7 +1052,7 @@ def main():
                 "placement_kept": spl.get("kept")})
     if per_rank:
         result["per_rank"] = per_rank
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)
