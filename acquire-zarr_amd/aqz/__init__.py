@@ -269,6 +269,12 @@ def lib():
         "aqz_compressor_scratch_bytes": ([C.POINTER(CompressionC), u64, u32, u32], u64),
         "aqz_compressor_run": ([vp, vp, u64, u32, vp, sz, vp, vp], i32),
         "aqz_compressor_blocksize": ([vp], u32),
+        "aqz_decompressor_create": ([u64, u32, C.POINTER(vp)], i32),
+        "aqz_decompressor_destroy": ([vp], None),
+        "aqz_decompressor_scratch_bytes": ([u64, u32], u64),
+        "aqz_decompressor_run": ([vp, vp, sz, vp, u32, vp, u64, u64, vp, vp], i32),
+        "aqz_stage_verify_layer": ([vp, u32, u64, vp, sz], i32),
+        "aqz_stage_verify_result": ([vp, u32, u64, C.POINTER(u32), C.POINTER(u32)], i32),
         "aqz_stage_bench_replace_rings": ([vp, u32], i32),
         "aqz_stage_bench_set_ring_offset": ([vp, u64], i32),
         "aqz_stage_bind_host_thread": ([vp], i32),
@@ -892,6 +898,18 @@ class Stage:
         self.wait_copies()
         return out[:int(off[-1])], off
 
+    # ---- on-device verification of a compressed layer ----------------------
+    def verify_layer(self, level, layer, frames_ptr=None, frames_bytes=0):
+        """(n_bad, first_bad): the layer's blosc-lz4 frames (the stage's own, or
+        the device copy at frames_ptr) decoded on the device and compared with
+        the resident chunks; first_bad is UINT32_MAX when every chunk verifies."""
+        _check(lib().aqz_stage_verify_layer(self.h, level, layer, frames_ptr, frames_bytes),
+               "verify_layer")
+        n, first = C.c_uint32(), C.c_uint32()
+        _check(lib().aqz_stage_verify_result(self.h, level, layer, C.byref(n),
+                                             C.byref(first)), "verify_result")
+        return n.value, first.value
+
 
 class Compressor:
     """blosc1/LZ4 frames of device-resident chunks (aqz_compressor_*)."""
@@ -924,6 +942,48 @@ class Compressor:
         _check(lib().aqz_compressor_run(self.h, chunks_ptr, pitch, n_chunks, dst_ptr,
                                         dst_cap, offsets_ptr, stream_ptr),
                "aqz_compressor_run")
+
+
+DECODE_OK, DECODE_SKIPPED, DECODE_BAD_HEADER, DECODE_CORRUPT, DECODE_UNSUPPORTED = range(5)
+AQZ_DECODE_OK, AQZ_DECODE_SKIPPED, AQZ_DECODE_BAD_HEADER = DECODE_OK, DECODE_SKIPPED, DECODE_BAD_HEADER
+AQZ_DECODE_CORRUPT, AQZ_DECODE_UNSUPPORTED = DECODE_CORRUPT, DECODE_UNSUPPORTED
+UINT32_MAX = (1 << 32) - 1
+
+
+def decompressor_scratch_bytes(max_chunk_bytes, max_chunks):
+    """Device bytes a Decompressor of these sizes allocates (no GPU needed)."""
+    return lib().aqz_decompressor_scratch_bytes(max_chunk_bytes, max_chunks)
+
+
+class Decompressor:
+    """Device decoder of blosc1/LZ4 frames (aqz_decompressor_*)."""
+
+    def __init__(self, max_chunk_bytes, max_chunks):
+        h = C.c_void_p()
+        _check(lib().aqz_decompressor_create(max_chunk_bytes, max_chunks, C.byref(h)),
+               "aqz_decompressor_create")
+        self.h = h
+        self.max_chunk_bytes = max_chunk_bytes
+        self.max_chunks = max_chunks
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.aqz_decompressor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def scratch_bytes(self, max_chunk_bytes=None, max_chunks=None):
+        return decompressor_scratch_bytes(
+            self.max_chunk_bytes if max_chunk_bytes is None else max_chunk_bytes,
+            self.max_chunks if max_chunks is None else max_chunks)
+
+    def run_ptr(self, frames_ptr, frames_bytes, offsets_ptr, n_chunks, dst_ptr, pitch,
+                chunk_bytes, status_ptr, stream_ptr=None):
+        _check(lib().aqz_decompressor_run(self.h, frames_ptr, frames_bytes, offsets_ptr,
+                                          n_chunks, dst_ptr, pitch, chunk_bytes, status_ptr,
+                                          stream_ptr), "aqz_decompressor_run")
 
 
 def shard_table(offsets, extents) -> bytes:

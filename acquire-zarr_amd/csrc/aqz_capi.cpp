@@ -30,6 +30,11 @@ struct aqz_compressor
     std::unique_ptr<Compressor> c;
     int32_t sticky = AQZ_STATUS_SUCCESS;
 };
+struct aqz_decompressor
+{
+    std::unique_ptr<Decompressor> d;
+    int32_t sticky = AQZ_STATUS_SUCCESS;
+};
 
 namespace {
 
@@ -1119,6 +1124,71 @@ aqz_compressor_run(aqz_compressor* c, const void* chunks, uint64_t pitch,
         c->c->run(static_cast<const uint8_t*>(chunks), pitch, n_chunks, nullptr, 0,
                   static_cast<uint8_t*>(dst), offsets, static_cast<hipStream_t>(stream));
     });
+}
+
+// ---- chunk decompression ---------------------------------------------------
+static_assert(AQZ_DECODE_OK == dec::kOk && AQZ_DECODE_SKIPPED == dec::kSkipped &&
+                AQZ_DECODE_BAD_HEADER == dec::kBadHeader &&
+                AQZ_DECODE_CORRUPT == dec::kCorrupt &&
+                AQZ_DECODE_UNSUPPORTED == dec::kUnsupported,
+              "decode status values");
+
+aqz_status
+aqz_decompressor_create(uint64_t max_chunk_bytes, uint32_t max_chunks, aqz_decompressor** out)
+{
+    if (!out)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    *out = nullptr;
+    return guard([&] {
+        auto h = std::make_unique<aqz_decompressor>();
+        h->d = std::make_unique<Decompressor>(max_chunk_bytes, max_chunks);
+        *out = h.release();
+    });
+}
+
+void
+aqz_decompressor_destroy(aqz_decompressor* d)
+{
+    delete d;
+}
+
+uint64_t
+aqz_decompressor_scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks)
+{
+    return Decompressor::scratch_bytes(max_chunk_bytes, max_chunks);
+}
+
+aqz_status
+aqz_decompressor_run(aqz_decompressor* d, const void* frames, size_t frames_bytes,
+                     const uint64_t* offsets, uint32_t n_chunks, void* dst, uint64_t pitch,
+                     uint64_t chunk_bytes, uint32_t* status, void* stream)
+{
+    if (!d || !frames || !offsets || !dst || !status)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    return guard_sticky(d, [&] {
+        d->d->run(static_cast<const uint8_t*>(frames), frames_bytes, offsets, n_chunks,
+                  static_cast<uint8_t*>(dst), pitch, chunk_bytes, status,
+                  static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer, const void* frames,
+                       size_t frames_bytes)
+{
+    return guard_sticky(st,
+                        [&] { st->st->verify_layer(level, layer, frames, frames_bytes); });
+}
+
+aqz_status
+aqz_stage_verify_result(aqz_stage* st, uint32_t level, uint64_t layer, uint32_t* n_bad,
+                        uint32_t* first_bad)
+{
+    if (!n_bad || !first_bad)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    *n_bad = 0;
+    *first_bad = UINT32_MAX;
+    return guard_sticky(st, [&] { st->st->verify_result(level, layer, n_bad, first_bad); });
 }
 
 // ---- shard packing ---------------------------------------------------------

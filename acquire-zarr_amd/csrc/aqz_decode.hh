@@ -1,0 +1,50 @@
+// aqz_decode.hh -- device decoder of blosc1 frames with the LZ4 codec (and
+// memcpyed frames): the inverse of aqz_codec.hh's blosc-lz4 row, for any
+// conforming frame (this library's 4 KiB streams or c-blosc's, any block
+// size, split or not, all three shuffle modes).  The parse and every bound
+// live in aqz_lz4dec.hh, shared with the host.
+//
+// A malformed frame is a status in status[], never a fault: reads end at
+// the frame's end, writes at the stream's end, and a bad frame stops only
+// its own workgroups.
+#pragma once
+
+#include "aqz_lz4dec.hh"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace aqz {
+
+// Bytes of decoded (still shuffled) blocks a workgroup keeps in LDS.  Frames
+// whose block size is at most this decode and un-shuffle without touching
+// global scratch (always true of this library's own frames: 4 KiB streams,
+// typesize <= 8); larger blocks decode into DecodeParams::scratch and a
+// second kernel un-shuffles them.
+constexpr uint32_t kDecodeLdsBytes = 32 * 1024;
+
+struct DecodeParams
+{
+    const uint8_t* frames;   // n_chunks frames back to back
+    uint64_t frames_bytes;
+    const uint64_t* offsets; // [n_chunks + 1] frame starts + total (device)
+    uint32_t n_chunks;
+    uint8_t* dst;            // frame q -> dst + slot(q) * pitch
+    uint64_t pitch;
+    uint64_t chunk_bytes;
+    uint32_t* status;        // [n_chunks] dec::k* per frame (by position q)
+    const uint32_t* order;   // slot(q) = order[q]; nullptr: q
+    // compare mode (bad != nullptr): dst is not written; bad[q] becomes 1
+    // when the decoded bytes differ from the chunk at dst (a zero-length
+    // frame: when that chunk is not all zero)
+    uint32_t* bad;
+    uint8_t* scratch;        // n_chunks * scratch_pitch bytes; nullptr: frames
+                             // with blocks above kDecodeLdsBytes are kUnsupported
+    uint64_t scratch_pitch;  // >= chunk_bytes, a multiple of 16
+};
+
+// Enqueue: status (and bad) cleared, frames decoded, large blocks un-shuffled.
+hipError_t launch_blosc_decode(const DecodeParams& p, hipStream_t stream);
+
+} // namespace aqz

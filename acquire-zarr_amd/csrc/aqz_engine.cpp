@@ -1011,6 +1011,9 @@ Stage::~Stage()
         for (hipEvent_t e : L.zin_ev)
             if (e)
                 (void)hipEventDestroy(e);
+        for (hipEvent_t e : L.verify_ev)
+            if (e)
+                (void)hipEventDestroy(e);
     }
 
     for (auto& pr : ev_pairs_) {
@@ -1386,6 +1389,11 @@ Stage::enter_layer(StageLevel& L, uint64_t layer)
     if (!L.copy_pending.empty() && L.copy_pending[slot]) {
         hip_check(hipStreamWaitEvent(stream_, L.copy_ev[slot], 0), "hipStreamWaitEvent");
         L.copy_pending[slot] = 0;
+    }
+    if (!L.verify_pending.empty() && L.verify_pending[slot]) {
+        // verify_layer's comparison still reads the slot
+        hip_check(hipStreamWaitEvent(stream_, L.verify_ev[slot], 0), "hipStreamWaitEvent");
+        L.verify_pending[slot] = 0;
     }
     if (!L.peer_ev.empty()) {
         // another stage's import of the slot, on any device
@@ -1902,6 +1910,12 @@ Stage::memory_usage() const
         f.device += L.d_zshuf.n;
         if (L.comp)
             f.device += L.comp->device_bytes();
+        if (L.dec)
+            f.device += L.dec->device_bytes();
+        for (const DevBuf& b : L.vwords)
+            f.device += b.n;
+        for (const PinnedBuf& b : L.h_vwords)
+            f.pinned += b.n;
     }
     for (int j = 0; j < 2; ++j) {
         f.device += d_stage_[j].n;
@@ -2438,6 +2452,7 @@ Stage::ensure_comp_slots(StageLevel& L)
     L.cdone_pending.assign(L.n_slots, 0);
     L.cdone_ticket.assign(L.n_slots, 0);
     L.comp_layer.assign(L.n_slots, -1);
+    L.comp_codec.assign(L.n_slots, 0);
     L.h_zin.resize(L.n_slots);
     L.h_zhas.resize(L.n_slots);
     L.zin_ev.assign(L.n_slots, nullptr);
@@ -2558,6 +2573,7 @@ Stage::compress_layer_host(StageLevel& L, uint32_t slot, uint64_t layer,
     host_zstd_compress(*zpool_, L.zjob[slot],
                        [ev = L.zin_ev[slot]] { (void)hipEventSynchronize(ev); });
     L.comp_layer[slot] = int64_t(layer);
+    L.comp_codec[slot] = c.codec;
     L.comp_host[slot] = 1;
 }
 
@@ -2625,6 +2641,129 @@ Stage::compress_layer(uint32_t level, uint64_t layer, const Compression& c)
     hip_check(hipEventRecord(L.copy_ev[slot], cs), "hipEventRecord");
     L.copy_pending[slot] = 1;
     L.comp_layer[slot] = int64_t(layer);
+    L.comp_codec[slot] = c.codec;
+}
+
+// ---- device decoder and on-device verification ----------------------------
+Decompressor::Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks)
+  : max_chunk_bytes_(max_chunk_bytes)
+  , max_chunks_(max_chunks)
+{
+    if (max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull || max_chunks == 0)
+        throw Error(1, "chunk size outside the blosc1 limits, or no chunks");
+    if (big_blocks) {
+        scratch_pitch_ = (max_chunk_bytes + 15) & ~uint64_t(15);
+        scratch_.alloc(scratch_bytes(max_chunk_bytes, max_chunks, true));
+    }
+}
+
+uint64_t
+Decompressor::scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks)
+{
+    if (!big_blocks || max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull)
+        return 0;
+    return ((max_chunk_bytes + 15) & ~uint64_t(15)) * max_chunks;
+}
+
+void
+Decompressor::run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                  uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+                  uint32_t* status, hipStream_t stream, const uint32_t* order, uint32_t* bad)
+{
+    if (chunk_bytes == 0 || chunk_bytes > max_chunk_bytes_)
+        throw Error(1, "chunk size above the decompressor's max_chunk_bytes");
+    if (n_chunks > max_chunks_)
+        throw Error(1, "more frames than the decompressor's max_chunks");
+    if (pitch < chunk_bytes)
+        throw Error(1, "chunk pitch below the chunk size");
+    DecodeParams p{};
+    p.frames = frames;
+    p.frames_bytes = frames_bytes;
+    p.offsets = offsets;
+    p.n_chunks = n_chunks;
+    p.dst = dst;
+    p.pitch = pitch;
+    p.chunk_bytes = chunk_bytes;
+    p.status = status;
+    p.order = order;
+    p.bad = bad;
+    p.scratch = scratch_.p;
+    p.scratch_pitch = scratch_pitch_;
+    hip_check(launch_blosc_decode(p, stream), "blosc decode launch");
+}
+
+void
+Stage::verify_layer(uint32_t level, uint64_t layer, const void* frames, size_t frames_bytes)
+{
+    if (level >= lv_.size())
+        throw Error(3, "level out of range");
+    StageLevel& L = lv_[level];
+    if (!L.ring.p)
+        throw Error(1, "level 0 is not split on the device by this stage");
+    const uint32_t slot = uint32_t(layer % L.n_slots);
+    if (L.slot_layer[slot] != int64_t(layer))
+        throw Error(1, "chunk layer not resident");
+    if (L.comp_layer.empty() || L.comp_layer[slot] != int64_t(layer))
+        throw Error(1, "layer was not compressed (or its slot was reused)");
+    if (L.comp_codec[slot] != 1)
+        throw Error(4, "only blosc-lz4 layers can be verified on the device");
+    const hipStream_t cs = comp_stream(L);
+    if (!L.dec) {
+        // the stage's own frames never have blocks above the LDS budget
+        // (kLz4StreamMax bytes per stream): no scratch copy of the layer
+        L.dec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false);
+        L.vwords.resize(L.n_slots);
+        L.h_vwords.resize(L.n_slots);
+        L.verify_ev.assign(L.n_slots, nullptr);
+        L.verify_pending.assign(L.n_slots, 0);
+        L.verify_layer.assign(L.n_slots, -1);
+        for (uint32_t s = 0; s < L.n_slots; ++s)
+            hip_check(hipEventCreateWithFlags(&L.verify_ev[s], hipEventDisableTiming),
+                      "hipEventCreate");
+    }
+    const size_t words = size_t(L.n_chunks) * 2 * 4;
+    if (L.verify_layer[slot] >= 0) // an earlier result of the slot may still be landing
+        hip_check(hipEventSynchronize(L.verify_ev[slot]), "hipEventSynchronize");
+    L.vwords[slot].alloc(words);
+    L.h_vwords[slot].alloc(words);
+    auto* status = reinterpret_cast<uint32_t*>(L.vwords[slot].p);
+    const uint8_t* fr = frames ? static_cast<const uint8_t*>(frames) : L.cframes[slot].p;
+    const uint64_t fb = frames ? uint64_t(frames_bytes) : uint64_t(L.cframes[slot].n);
+    // in order behind the compression on its stream; the offsets are the
+    // layer's own (device copy), whichever frames are decoded
+    L.dec->run(fr, fb, reinterpret_cast<const uint64_t*>(L.coffsets[slot].p), L.n_chunks,
+               L.ring.p + slot * L.slot_bytes, L.pitch, L.bpc, status, cs,
+               reinterpret_cast<const uint32_t*>(L.shard_order.p), status + L.n_chunks);
+    hip_check(hipMemcpyAsync(L.h_vwords[slot].p, L.vwords[slot].p, words, hipMemcpyDeviceToHost,
+                             cs),
+              "hipMemcpyAsync");
+    hip_check(hipEventRecord(L.verify_ev[slot], cs), "hipEventRecord");
+    L.verify_pending[slot] = 1;
+    L.verify_layer[slot] = int64_t(layer);
+}
+
+void
+Stage::verify_result(uint32_t level, uint64_t layer, uint32_t* n_bad, uint32_t* first_bad)
+{
+    if (level >= lv_.size())
+        throw Error(3, "level out of range");
+    StageLevel& L = lv_[level];
+    const uint32_t slot = L.n_slots ? uint32_t(layer % L.n_slots) : 0;
+    if (L.verify_layer.empty() || L.verify_layer[slot] != int64_t(layer))
+        throw Error(1, "layer was not verified (or its slot was reused)");
+    hip_check(hipEventSynchronize(L.verify_ev[slot]), "hipEventSynchronize");
+    const auto* status = reinterpret_cast<const uint32_t*>(L.h_vwords[slot].p);
+    const uint32_t* bad = status + L.n_chunks;
+    uint32_t n = 0, first = UINT32_MAX;
+    for (uint32_t q = 0; q < L.n_chunks; ++q) {
+        if (status[q] <= dec::kSkipped && !bad[q])
+            continue;
+        const uint32_t chunk = L.h_order.empty() ? q : L.h_order[q];
+        ++n;
+        first = std::min(first, chunk);
+    }
+    *n_bad = n;
+    *first_bad = first;
 }
 
 void

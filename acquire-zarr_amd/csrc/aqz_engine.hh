@@ -9,6 +9,7 @@
 #pragma once
 
 #include "aqz_codec.hh"
+#include "aqz_decode.hh"
 #include "aqz_copy.hh"
 #include "aqz_geometry.hh"
 #include "aqz_hostsplit.hh"
@@ -212,6 +213,36 @@ class Compressor
     DevBuf lits_, seqs_, snseq_, snlit_, stail_, bltype_, bseqb_, bnlit_, seqt_, far_;
 };
 
+// Device decoder of blosc1-lz4 (and memcpyed) frames (aqz_decode.hip): the
+// frames of n_chunks chunks back to back in device memory -> chunk i at
+// dst + i * pitch and a status word per frame.
+class Decompressor
+{
+  public:
+    // big_blocks: keep a scratch slot per chunk for frames whose blocks do
+    // not fit the LDS budget (kDecodeLdsBytes; c-blosc's own frames).
+    // Without it such frames get the status dec::kUnsupported.
+    Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks = true);
+    // device bytes a Decompressor(max_chunk_bytes, max_chunks) allocates
+    static uint64_t scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks,
+                                  bool big_blocks = true);
+    // Enqueue on `stream`.  order (device, optional): frame position -> chunk
+    // slot of dst.  bad (device, optional, n_chunks words): compare mode --
+    // dst is read, not written, and bad[q] = 1 where frame q does not
+    // decode to the chunk at dst.
+    void run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+             uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+             uint32_t* status, hipStream_t stream, const uint32_t* order = nullptr,
+             uint32_t* bad = nullptr);
+    uint64_t device_bytes() const { return scratch_.n; }
+
+  private:
+    uint64_t max_chunk_bytes_;
+    uint32_t max_chunks_;
+    uint64_t scratch_pitch_ = 0;
+    DevBuf scratch_;
+};
+
 struct ArrayDesc
 {
     std::vector<Dim> dims; // acquisition order
@@ -346,6 +377,17 @@ struct StageLevel
     std::vector<uint8_t> cdone_pending;
     std::vector<uint64_t> cdone_ticket;    // ... by this DMA-engine ticket (0: none)
     std::vector<int64_t> comp_layer;       // layer compressed in each slot
+    std::vector<int32_t> comp_codec;       // ... and with which codec
+    // on-device verification of compressed layers (verify_layer), allocated
+    // by the first verify call: the decoder, per slot the frame statuses
+    // and mismatch words ([status n_chunks][bad n_chunks], device and pinned
+    // host copy), the event after the read-back and the layer verified
+    std::unique_ptr<Decompressor> dec;
+    std::vector<DevBuf> vwords;
+    std::vector<PinnedBuf> h_vwords;
+    std::vector<hipEvent_t> verify_ev;
+    std::vector<uint8_t> verify_pending;   // the slot's next layer waits for verify_ev
+    std::vector<int64_t> verify_layer;
     // host-side zstd codecs (aqz_hostzstd.hh): per slot the pinned inputs
     // (shuffled or raw chunks, has_data bytes), their D2H event and the
     // host job; comp_host[slot] = the slot's compression ran on the host
@@ -439,6 +481,13 @@ class Stage
     void compressed_entries(uint32_t level, uint64_t layer, ChunkEntry* out, size_t n);
     void shard_geometry(uint32_t level, uint32_t* chunks_per_shard, uint32_t* n_shards,
                         uint32_t* layers_per_shard) const;
+    // decode the frames of a compressed (blosc-lz4), still resident layer on
+    // the device and compare them with the resident chunks, on the stream
+    // that compressed it.  frames == nullptr: the stage's own frames;
+    // otherwise a device copy of them (same order, same offsets).
+    void verify_layer(uint32_t level, uint64_t layer, const void* frames, size_t frames_bytes);
+    // waits; chunks that did not verify and the lowest such chunk index
+    void verify_result(uint32_t level, uint64_t layer, uint32_t* n_bad, uint32_t* first_bad);
     void finalize();
     // the level-0 tile split on the host (level0_on_host; aqz_hostsplit.hh):
     // frames [first, first + n) over the stage's host threads, or rows of

@@ -609,6 +609,70 @@ aqz_status aqz_dims_split_frame_rows(const aqz_dims* d, const void* frame, uint6
  * The unpaired trailing z plane is dropped, as in the reference. */
 aqz_status aqz_stage_finalize(aqz_stage* st);
 
+/* ---- chunk decompression on the device ------------------------------------
+ * The inverse of AQZ_CODEC_BLOSC_LZ4: blosc1 frames with the LZ4 codec, and
+ * memcpyed frames, decoded where they lie in HBM.  The format contract is the
+ * codec metadata the reference writes (array.cpp:340-360: "blosc", cname
+ * "lz4", clevel, shuffle, typesize, blocksize 0): any conforming blosc1 v2
+ * frame is accepted -- this library's (4 KiB streams) or c-blosc's own (any
+ * block size, split or "don't split", byte shuffle, bitshuffle or none,
+ * streams stored raw).  The reference has no read path; what a reader of its
+ * output would run per chunk is blosc_decompress_ctx.
+ * A malformed frame is a per-chunk status, never a fault: reads end at the
+ * frame's end, writes at the chunk's end, and the other frames of the run
+ * are decoded as if it were not there. */
+#define AQZ_DECODE_OK 0          /* the chunk holds the decoded bytes */
+#define AQZ_DECODE_SKIPPED 1     /* zero-length frame: the chunk was zero-filled (an
+                                    unwritten chunk reads as fill_value 0, array.cpp:279) */
+#define AQZ_DECODE_BAD_HEADER 2  /* version, typesize 0, nbytes != chunk_bytes, cbytes !=
+                                    frame size, blocksize 0 or no multiple of typesize, a
+                                    block start outside the frame, or offsets that do not
+                                    describe a frame inside frames_bytes */
+#define AQZ_DECODE_CORRUPT 3     /* a stream record or an LZ4 sequence leaves its bounds */
+#define AQZ_DECODE_UNSUPPORTED 4 /* not the LZ4 codec: blosc-zstd frames, plain zstd frames */
+typedef struct aqz_decompressor aqz_decompressor;
+/* A decoder with device scratch for runs of up to max_chunks frames of up to
+ * max_chunk_bytes each (aqz_decompressor_scratch_bytes). */
+aqz_status aqz_decompressor_create(uint64_t max_chunk_bytes, uint32_t max_chunks,
+                                   aqz_decompressor** out);
+void aqz_decompressor_destroy(aqz_decompressor* d);
+/* Device bytes aqz_decompressor_create allocates: one slot per chunk, used by
+ * frames whose blocks exceed the on-chip budget (32 KiB; c-blosc's frames of
+ * large chunks).  0 on invalid sizes.  No GPU needed. */
+uint64_t aqz_decompressor_scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks);
+/* Decode n_chunks frames lying back to back at frames (device, frames_bytes
+ * in all): frame i is bytes [offsets[i], offsets[i + 1]) -- offsets (device,
+ * n_chunks + 1 uint64) as aqz_compressor_run and aqz_stage_compress_layer
+ * write them; a zero-length frame is a skipped chunk.  Chunk i goes to
+ * dst + i * pitch (device; chunk_bytes each, pitch >= chunk_bytes; the bytes
+ * between chunks are not touched) and its AQZ_DECODE_* status to status[i]
+ * (device).  Typesize and shuffle come from each frame's header.  Enqueued
+ * on `stream` (hipStream_t; NULL = default); returns at once.  The contents
+ * of a chunk whose status is an error are unspecified. */
+aqz_status aqz_decompressor_run(aqz_decompressor* d, const void* frames, size_t frames_bytes,
+                                const uint64_t* offsets, uint32_t n_chunks, void* dst,
+                                uint64_t pitch, uint64_t chunk_bytes, uint32_t* status,
+                                void* stream);
+
+/* Decode the frames of compressed layer `layer` of `level` on the device and compare them
+ * with the resident chunk layer.  frames == NULL: the stage's own compressed buffer.
+ * Otherwise frames is a device copy in the same output order and with the same offsets
+ * (e.g. after a round trip through the sink).  Enqueued on the hand-off stream after the
+ * compression (the stream aqz_stage_compress_layer runs on).  The slot is not reused until
+ * the comparison has read it.  The layer must have been compressed with AQZ_CODEC_BLOSC_LZ4
+ * (any clevel) and still be resident (else AQZ_STATUS_INVALID_ARGUMENT); layers compressed
+ * with a zstd codec return AQZ_STATUS_NOT_YET_IMPLEMENTED.  The first call of a stage
+ * allocates the decoder state (two words per chunk and slot, device and pinned; no copy of
+ * the layer: the comparison happens as the blocks are un-shuffled), which
+ * aqz_stage_memory_usage reports from then on. */
+aqz_status aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer,
+                                  const void* frames, size_t frames_bytes);
+/* Waits.  *n_bad = chunks whose decoded bytes differ from the resident chunk or whose
+ * decode status is an error.  A skipped chunk is good iff the resident chunk is all zero.
+ * *first_bad = lowest such chunk index (aqz_chunk_entry.chunk), UINT32_MAX if none. */
+aqz_status aqz_stage_verify_result(aqz_stage* st, uint32_t level, uint64_t layer,
+                                   uint32_t* n_bad, uint32_t* first_bad);
+
 #ifdef __cplusplus
 }
 #endif

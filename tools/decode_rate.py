@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Dev harness (not product): rates of the device blosc1-LZ4 decoder and of
+the stage's on-device verification, next to the device compressor's rate on
+the same data and c-blosc's one-core decode of the same frames on this host.
+
+One C2-shaped chunk layer: 512 MiB of camera-like u16 in 64 chunks of
+256x256x64 (8 MiB), lz4 clevel 5, byte shuffle and bitshuffle.  Everything is
+timed in this one process after a warm-up run of each call:
+
+  aqz_compressor_run, aqz_decompressor_run   HIP events on the stream they are
+                                             enqueued on, `--reps` calls each
+  aqz_stage_verify_layer + _verify_result    the stage enqueues on its own
+                                             hand-off stream, so a host clock
+                                             around the pair (it ends in the
+                                             wait of verify_result)
+  c-blosc                                    blosc_decompress_ctx, one thread,
+                                             over `--host-chunks` frames
+
+Rates are GB/s (1e9) of uncompressed bytes.  One JSON line per shuffle mode:
+
+  python3 tools/decode_rate.py [--reps 10] [--out profiles/r07_decode_rate.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "acquire-zarr_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+import aqz  # noqa: E402
+import torch  # noqa: E402
+
+N_CHUNKS, CHUNK = 64, 256 * 256 * 64 * 2
+SIDE, PLANES = 2048, 64          # 8 x 8 chunks of 256 x 256, 64 planes deep
+
+
+def camera(dev):
+    n_px = N_CHUNKS * CHUNK // 2
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    x = torch.arange(n_px, device=dev, dtype=torch.float32)
+    v = 1000.0 + 200.0 * torch.sin(x / 977.0) + 30.0 * torch.randn(n_px, device=dev, generator=g)
+    return v.clamp(0, 65535).to(torch.int32).to(torch.int16).view(torch.uint8)
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--host-chunks", type=int, default=8)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r07_decode_rate.jsonl"))
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    src = camera(dev)
+    layer_bytes = N_CHUNKS * CHUNK
+    gbs = lambda ms: round(layer_bytes / ms / 1e6, 1)
+    try:
+        from codec_helpers import libblosc, libblosc_decode
+        have_blosc = libblosc() is not None
+    except Exception:
+        have_blosc = False
+    rows = []
+    for shuffle in (1, 2):
+        comp = aqz.Compressor(CHUNK, 2, clevel=5, shuffle=shuffle)
+        cap = comp.max_bytes(N_CHUNKS)
+        frames = torch.empty(cap, dtype=torch.uint8, device=dev)
+        off = torch.empty(N_CHUNKS + 1, dtype=torch.int64, device=dev)
+        c_ms = timed(lambda: comp.run_ptr(src.data_ptr(), CHUNK, N_CHUNKS, frames.data_ptr(), cap,
+                                          off.data_ptr(), stream), args.reps)
+        total = int(off[-1].item())
+        dec = aqz.Decompressor(CHUNK, N_CHUNKS)
+        out = torch.empty(layer_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(N_CHUNKS, dtype=torch.int32, device=dev)
+        d_ms = timed(lambda: dec.run_ptr(frames.data_ptr(), cap, off.data_ptr(), N_CHUNKS,
+                                         out.data_ptr(), CHUNK, CHUNK, status.data_ptr(), stream),
+                     args.reps)
+        exact = bool(torch.equal(out, src)) and not bool(status.any())
+        row = {"tool": "tools/decode_rate.py", "layer": "C2 level 0: 64 chunks of 256x256x64 u16",
+               "layer_bytes": layer_bytes, "codec": "blosc-lz4", "clevel": 5, "shuffle": shuffle,
+               "blocksize": comp.blocksize, "compressed_bytes": total,
+               "ratio": round(layer_bytes / total, 3), "reps": args.reps,
+               "compress_ms": round(c_ms, 3), "compress_gbs": gbs(c_ms),
+               "decode_ms": round(d_ms, 3), "decode_gbs": gbs(d_ms), "decode_exact": exact}
+        if have_blosc:
+            o = off.cpu().numpy()
+            k = min(args.host_chunks, N_CHUNKS)
+            host = [frames[int(o[i]):int(o[i + 1])].cpu().numpy().tobytes() for i in range(k)]
+            libblosc_decode(host[0])
+            t0 = time.perf_counter()
+            for fr in host:
+                libblosc_decode(fr)
+            dt = time.perf_counter() - t0
+            row["cblosc_1core_decode_gbs"] = round(k * CHUNK / dt / 1e9, 2)
+            row["cblosc_chunks"] = k
+        dec.close()
+        comp.close()
+        del frames, out
+
+        # the same layer through a stage: appended from the device, compressed
+        # on the hand-off stream, then verified against the resident chunks
+        dims = [(aqz.TIME, 0, PLANES, 1), (aqz.SPACE, SIDE, 256, 1),
+                (aqz.SPACE, SIDE, 256, 1)]
+        st = aqz.Stage(dims, aqz.UINT16, aqz.MEAN, multiscale=False, layer_slots=1,
+                       max_batch_frames=PLANES)
+        st.append_ptr(src.data_ptr(), PLANES, aqz.MEM_DEVICE)
+        st.synchronize()
+        st.compress_layer(0, 0, clevel=5, shuffle=shuffle)
+        st.compressed_offsets(0, 0)
+        res = st.verify_layer(0, 0)     # warm-up (allocates the decoder state)
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            res = st.verify_layer(0, 0)
+        v_ms = (time.perf_counter() - t0) * 1e3 / args.reps
+        row.update({"verify_ms": round(v_ms, 3), "verify_gbs": gbs(v_ms),
+                    "verify_result": list(res),
+                    "verify_timing": "host clock around verify_layer + verify_result"})
+        st.close()
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        for row in rows:
+            f.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
