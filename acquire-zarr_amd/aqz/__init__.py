@@ -270,8 +270,11 @@ def lib():
         "aqz_compressor_run": ([vp, vp, u64, u32, vp, sz, vp, vp], i32),
         "aqz_compressor_blocksize": ([vp], u32),
         "aqz_decompressor_create": ([u64, u32, C.POINTER(vp)], i32),
+        "aqz_decompressor_create_for": ([u64, u32, u32, C.POINTER(vp)], i32),
         "aqz_decompressor_destroy": ([vp], None),
         "aqz_decompressor_scratch_bytes": ([u64, u32], u64),
+        "aqz_decompressor_scratch_bytes_for": ([u64, u32, u32], u64),
+        "aqz_stage_verify_prepare": ([vp, u32], i32),
         "aqz_decompressor_run": ([vp, vp, sz, vp, u32, vp, u64, u64, vp, vp], i32),
         "aqz_stage_verify_layer": ([vp, u32, u64, vp, sz], i32),
         "aqz_stage_verify_result": ([vp, u32, u64, C.POINTER(u32), C.POINTER(u32)], i32),
@@ -899,10 +902,17 @@ class Stage:
         return out[:int(off[-1])], off
 
     # ---- on-device verification of a compressed layer ----------------------
+    def verify_prepare(self, codecs):
+        """Allocate now the decoder state verify_layer needs for layers of the
+        codecs listed (DECODE_CODEC_* or-ed); zstd layers verify only after it."""
+        _check(lib().aqz_stage_verify_prepare(self.h, codecs), "verify_prepare")
+
     def verify_layer(self, level, layer, frames_ptr=None, frames_bytes=0):
-        """(n_bad, first_bad): the layer's blosc-lz4 frames (the stage's own, or
-        the device copy at frames_ptr) decoded on the device and compared with
-        the resident chunks; first_bad is UINT32_MAX when every chunk verifies."""
+        """(n_bad, first_bad): the layer's blosc-lz4 frames -- after
+        verify_prepare(DECODE_CODEC_ZSTD) also blosc-zstd and zstd frames -- (the
+        stage's own, or the device copy at frames_ptr) decoded on the device and
+        compared with the resident chunks; first_bad is UINT32_MAX when every
+        chunk verifies."""
         _check(lib().aqz_stage_verify_layer(self.h, level, layer, frames_ptr, frames_bytes),
                "verify_layer")
         n, first = C.c_uint32(), C.c_uint32()
@@ -947,24 +957,36 @@ class Compressor:
 DECODE_OK, DECODE_SKIPPED, DECODE_BAD_HEADER, DECODE_CORRUPT, DECODE_UNSUPPORTED = range(5)
 AQZ_DECODE_OK, AQZ_DECODE_SKIPPED, AQZ_DECODE_BAD_HEADER = DECODE_OK, DECODE_SKIPPED, DECODE_BAD_HEADER
 AQZ_DECODE_CORRUPT, AQZ_DECODE_UNSUPPORTED = DECODE_CORRUPT, DECODE_UNSUPPORTED
+DECODE_CODEC_LZ4, DECODE_CODEC_ZSTD = 1, 2
+AQZ_DECODE_CODEC_LZ4, AQZ_DECODE_CODEC_ZSTD = DECODE_CODEC_LZ4, DECODE_CODEC_ZSTD
 UINT32_MAX = (1 << 32) - 1
 
 
-def decompressor_scratch_bytes(max_chunk_bytes, max_chunks):
-    """Device bytes a Decompressor of these sizes allocates (no GPU needed)."""
-    return lib().aqz_decompressor_scratch_bytes(max_chunk_bytes, max_chunks)
+def decompressor_scratch_bytes(max_chunk_bytes, max_chunks, codecs=DECODE_CODEC_LZ4):
+    """Device bytes a Decompressor of these sizes and codecs allocates (no GPU
+    needed)."""
+    if codecs == DECODE_CODEC_LZ4:
+        return lib().aqz_decompressor_scratch_bytes(max_chunk_bytes, max_chunks)
+    return lib().aqz_decompressor_scratch_bytes_for(max_chunk_bytes, max_chunks, codecs)
 
 
 class Decompressor:
-    """Device decoder of blosc1/LZ4 frames (aqz_decompressor_*)."""
+    """Device decoder of blosc1/LZ4 frames and, with DECODE_CODEC_ZSTD, of
+    blosc1/zstd and plain zstd frames (aqz_decompressor_*)."""
 
-    def __init__(self, max_chunk_bytes, max_chunks):
+    def __init__(self, max_chunk_bytes, max_chunks, codecs=DECODE_CODEC_LZ4):
         h = C.c_void_p()
-        _check(lib().aqz_decompressor_create(max_chunk_bytes, max_chunks, C.byref(h)),
-               "aqz_decompressor_create")
+        if codecs == DECODE_CODEC_LZ4:
+            _check(lib().aqz_decompressor_create(max_chunk_bytes, max_chunks, C.byref(h)),
+                   "aqz_decompressor_create")
+        else:
+            _check(lib().aqz_decompressor_create_for(max_chunk_bytes, max_chunks, codecs,
+                                                     C.byref(h)),
+                   "aqz_decompressor_create_for")
         self.h = h
         self.max_chunk_bytes = max_chunk_bytes
         self.max_chunks = max_chunks
+        self.codecs = codecs
 
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
@@ -977,7 +999,7 @@ class Decompressor:
     def scratch_bytes(self, max_chunk_bytes=None, max_chunks=None):
         return decompressor_scratch_bytes(
             self.max_chunk_bytes if max_chunk_bytes is None else max_chunk_bytes,
-            self.max_chunks if max_chunks is None else max_chunks)
+            self.max_chunks if max_chunks is None else max_chunks, self.codecs)
 
     def run_ptr(self, frames_ptr, frames_bytes, offsets_ptr, n_chunks, dst_ptr, pitch,
                 chunk_bytes, status_ptr, stream_ptr=None):

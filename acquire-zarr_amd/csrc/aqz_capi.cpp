@@ -1146,6 +1146,25 @@ aqz_decompressor_create(uint64_t max_chunk_bytes, uint32_t max_chunks, aqz_decom
     });
 }
 
+static_assert(AQZ_DECODE_CODEC_LZ4 == dec::kFamilyLz4 && AQZ_DECODE_CODEC_ZSTD == dec::kFamilyZstd,
+              "decode codec bits");
+
+aqz_status
+aqz_decompressor_create_for(uint64_t max_chunk_bytes, uint32_t max_chunks, uint32_t codecs,
+                            aqz_decompressor** out)
+{
+    if (!out)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (codecs == 0 || (codecs & ~(AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD)))
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    return guard([&] {
+        auto h = std::make_unique<aqz_decompressor>();
+        h->d = std::make_unique<Decompressor>(max_chunk_bytes, max_chunks, true, codecs);
+        *out = h.release();
+    });
+}
+
 void
 aqz_decompressor_destroy(aqz_decompressor* d)
 {
@@ -1156,6 +1175,12 @@ uint64_t
 aqz_decompressor_scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks)
 {
     return Decompressor::scratch_bytes(max_chunk_bytes, max_chunks);
+}
+
+uint64_t
+aqz_decompressor_scratch_bytes_for(uint64_t max_chunk_bytes, uint32_t max_chunks, uint32_t codecs)
+{
+    return Decompressor::scratch_bytes(max_chunk_bytes, max_chunks, true, codecs);
 }
 
 aqz_status
@@ -1178,6 +1203,14 @@ aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer, const void
 {
     return guard_sticky(st,
                         [&] { st->st->verify_layer(level, layer, frames, frames_bytes); });
+}
+
+aqz_status
+aqz_stage_verify_prepare(aqz_stage* st, uint32_t codecs)
+{
+    if (codecs == 0 || (codecs & ~(AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD)))
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    return guard_sticky(st, [&] { st->st->verify_prepare(codecs); });
 }
 
 aqz_status

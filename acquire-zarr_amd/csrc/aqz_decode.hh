@@ -42,9 +42,30 @@ struct DecodeParams
     uint8_t* scratch;        // n_chunks * scratch_pitch bytes; nullptr: frames
                              // with blocks above kDecodeLdsBytes are kUnsupported
     uint64_t scratch_pitch;  // >= chunk_bytes, a multiple of 16
+    // codec families of the run (dec::kFamily*); 0 = kFamilyLz4.  Frames of a
+    // family that is not listed get kUnsupported; with kFamilyZstd listed,
+    // launch_blosc_decode leaves zstd frames to launch_zstd_decode
+    // (aqz_zstddec.hip), which runs behind it on the same stream.
+    uint32_t codecs;
+    // launch_zstd_decode only: Huffman literals of the block a workgroup
+    // decodes, zlit_pitch bytes per (chunk, pass), zpasses passes per chunk.
+    // scratch must be set (staging of shuffled blocks and of compare mode).
+    uint8_t* zlit;
+    uint64_t zlit_pitch;
+    uint32_t zpasses;
 };
 
 // Enqueue: status (and bad) cleared, frames decoded, large blocks un-shuffled.
 hipError_t launch_blosc_decode(const DecodeParams& p, hipStream_t stream);
+
+// Passes per chunk and literal bytes per pass launch_zstd_decode needs for
+// chunks of up to max_chunk_bytes.
+constexpr uint32_t kZstdMaxPasses = 8;
+uint32_t zstd_decode_passes(uint64_t max_chunk_bytes);
+uint64_t zstd_decode_lit_pitch(uint64_t max_chunk_bytes);
+// Enqueue behind launch_blosc_decode (which cleared status and bad): the
+// run's zstd frames -- plain zstd, blosc1 with the zstd codec (memcpyed ones
+// included) -- decoded; other frames are not touched.
+hipError_t launch_zstd_decode(const DecodeParams& p, hipStream_t stream);
 
 } // namespace aqz

@@ -1912,6 +1912,9 @@ Stage::memory_usage() const
             f.device += L.comp->device_bytes();
         if (L.dec)
             f.device += L.dec->device_bytes();
+        if (L.zdec)
+            f.device += L.zdec->device_bytes();
+        f.device += L.voffsets.n;
         for (const DevBuf& b : L.vwords)
             f.device += b.n;
         for (const PinnedBuf& b : L.h_vwords)
@@ -2645,24 +2648,43 @@ Stage::compress_layer(uint32_t level, uint64_t layer, const Compression& c)
 }
 
 // ---- device decoder and on-device verification ----------------------------
-Decompressor::Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks)
+Decompressor::Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks,
+                           uint32_t codecs)
   : max_chunk_bytes_(max_chunk_bytes)
   , max_chunks_(max_chunks)
+  , codecs_(codecs)
 {
     if (max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull || max_chunks == 0)
         throw Error(1, "chunk size outside the blosc1 limits, or no chunks");
-    if (big_blocks) {
+    if (codecs == 0 || (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd)))
+        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD");
+    const bool zstd = codecs & dec::kFamilyZstd;
+    if (big_blocks || zstd) {
         scratch_pitch_ = (max_chunk_bytes + 15) & ~uint64_t(15);
-        scratch_.alloc(scratch_bytes(max_chunk_bytes, max_chunks, true));
+        scratch_.alloc(scratch_pitch_ * max_chunks);
+    }
+    if (zstd) {
+        zpasses_ = zstd_decode_passes(max_chunk_bytes);
+        zlit_pitch_ = zstd_decode_lit_pitch(max_chunk_bytes);
+        zlit_.alloc(zlit_pitch_ * zpasses_ * max_chunks);
     }
 }
 
 uint64_t
-Decompressor::scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks)
+Decompressor::scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks,
+                            uint32_t codecs)
 {
-    if (!big_blocks || max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull)
+    if (max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull || codecs == 0 ||
+        (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd)))
         return 0;
-    return ((max_chunk_bytes + 15) & ~uint64_t(15)) * max_chunks;
+    const bool zstd = codecs & dec::kFamilyZstd;
+    uint64_t n = 0;
+    if (big_blocks || zstd)
+        n += ((max_chunk_bytes + 15) & ~uint64_t(15)) * max_chunks;
+    if (zstd)
+        n += zstd_decode_lit_pitch(max_chunk_bytes) * zstd_decode_passes(max_chunk_bytes) *
+             max_chunks;
+    return n;
 }
 
 void
@@ -2689,7 +2711,54 @@ Decompressor::run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* 
     p.bad = bad;
     p.scratch = scratch_.p;
     p.scratch_pitch = scratch_pitch_;
+    p.codecs = codecs_;
+    p.zlit = zlit_.p;
+    p.zlit_pitch = zlit_pitch_;
+    p.zpasses = zpasses_;
+    // clears the status words and takes the LZ4, memcpyed and zero-length frames
     hip_check(launch_blosc_decode(p, stream), "blosc decode launch");
+    if (codecs_ & dec::kFamilyZstd)
+        hip_check(launch_zstd_decode(p, stream), "zstd decode launch");
+}
+
+// per slot: the word buffers (allocated by the first use), the event and the
+// layer verified
+static void
+ensure_verify_slots(StageLevel& L)
+{
+    if (!L.verify_ev.empty())
+        return;
+    L.vwords.resize(L.n_slots);
+    L.h_vwords.resize(L.n_slots);
+    L.verify_ev.assign(L.n_slots, nullptr);
+    L.verify_pending.assign(L.n_slots, 0);
+    L.verify_layer.assign(L.n_slots, -1);
+    for (uint32_t s = 0; s < L.n_slots; ++s)
+        hip_check(hipEventCreateWithFlags(&L.verify_ev[s], hipEventDisableTiming),
+                  "hipEventCreate");
+}
+
+void
+Stage::verify_prepare(uint32_t codecs)
+{
+    if (codecs == 0 || (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd)))
+        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD");
+    for (StageLevel& L : lv_) {
+        if (!L.ring.p)
+            continue;
+        ensure_verify_slots(L);
+        if ((codecs & dec::kFamilyLz4) && !L.dec)
+            L.dec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false);
+        if ((codecs & dec::kFamilyZstd) && !L.zdec) {
+            L.zdec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false, dec::kFamilyZstd);
+            L.voffsets.alloc((size_t(L.n_chunks) + 1) * 8);
+        }
+        const size_t words = size_t(L.n_chunks) * 2 * 4;
+        for (uint32_t s = 0; s < L.n_slots; ++s) {
+            L.vwords[s].alloc(words);
+            L.h_vwords[s].alloc(words);
+        }
+    }
 }
 
 void
@@ -2705,21 +2774,19 @@ Stage::verify_layer(uint32_t level, uint64_t layer, const void* frames, size_t f
         throw Error(1, "chunk layer not resident");
     if (L.comp_layer.empty() || L.comp_layer[slot] != int64_t(layer))
         throw Error(1, "layer was not compressed (or its slot was reused)");
-    if (L.comp_codec[slot] != 1)
-        throw Error(4, "only blosc-lz4 layers can be verified on the device");
+    const int32_t codec = L.comp_codec[slot];
+    const bool zstd = codec == 2 || codec == 3;
+    if (codec != 1 && !(zstd && L.zdec))
+        throw Error(4, "zstd layers are verified on the device after verify_prepare; "
+                       "other codecs never");
+    if (zstd && L.comp_host[slot] && !frames)
+        throw Error(1, "the layer's frames were made on the host: pass a device copy");
     const hipStream_t cs = comp_stream(L);
-    if (!L.dec) {
+    if (!zstd && !L.dec) {
         // the stage's own frames never have blocks above the LDS budget
         // (kLz4StreamMax bytes per stream): no scratch copy of the layer
         L.dec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false);
-        L.vwords.resize(L.n_slots);
-        L.h_vwords.resize(L.n_slots);
-        L.verify_ev.assign(L.n_slots, nullptr);
-        L.verify_pending.assign(L.n_slots, 0);
-        L.verify_layer.assign(L.n_slots, -1);
-        for (uint32_t s = 0; s < L.n_slots; ++s)
-            hip_check(hipEventCreateWithFlags(&L.verify_ev[s], hipEventDisableTiming),
-                      "hipEventCreate");
+        ensure_verify_slots(L);
     }
     const size_t words = size_t(L.n_chunks) * 2 * 4;
     if (L.verify_layer[slot] >= 0) // an earlier result of the slot may still be landing
@@ -2731,9 +2798,20 @@ Stage::verify_layer(uint32_t level, uint64_t layer, const void* frames, size_t f
     const uint64_t fb = frames ? uint64_t(frames_bytes) : uint64_t(L.cframes[slot].n);
     // in order behind the compression on its stream; the offsets are the
     // layer's own (device copy), whichever frames are decoded
-    L.dec->run(fr, fb, reinterpret_cast<const uint64_t*>(L.coffsets[slot].p), L.n_chunks,
-               L.ring.p + slot * L.slot_bytes, L.pitch, L.bpc, status, cs,
-               reinterpret_cast<const uint32_t*>(L.shard_order.p), status + L.n_chunks);
+    const uint64_t* offs = reinterpret_cast<const uint64_t*>(L.coffsets[slot].p);
+    if (L.comp_host[slot]) { // the host job's offsets: copied up
+        HostLayerJob& j = *L.zjob[slot];
+        j.wait();
+        if (j.status)
+            throw Error(j.status, "zstd compression failed");
+        hip_check(hipMemcpyAsync(L.voffsets.p, j.offsets.data(), (size_t(L.n_chunks) + 1) * 8,
+                                 hipMemcpyHostToDevice, cs),
+                  "hipMemcpyAsync");
+        offs = reinterpret_cast<const uint64_t*>(L.voffsets.p);
+    }
+    (zstd ? L.zdec : L.dec)
+      ->run(fr, fb, offs, L.n_chunks, L.ring.p + slot * L.slot_bytes, L.pitch, L.bpc, status, cs,
+            reinterpret_cast<const uint32_t*>(L.shard_order.p), status + L.n_chunks);
     hip_check(hipMemcpyAsync(L.h_vwords[slot].p, L.vwords[slot].p, words, hipMemcpyDeviceToHost,
                              cs),
               "hipMemcpyAsync");

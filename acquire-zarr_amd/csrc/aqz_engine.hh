@@ -213,19 +213,24 @@ class Compressor
     DevBuf lits_, seqs_, snseq_, snlit_, stail_, bltype_, bseqb_, bnlit_, seqt_, far_;
 };
 
-// Device decoder of blosc1-lz4 (and memcpyed) frames (aqz_decode.hip): the
-// frames of n_chunks chunks back to back in device memory -> chunk i at
-// dst + i * pitch and a status word per frame.
+// Device decoder of blosc1-lz4 (and memcpyed) frames (aqz_decode.hip) and,
+// when created for them, of blosc1-zstd and plain zstd frames
+// (aqz_zstddec.hip): the frames of n_chunks chunks back to back in device
+// memory -> chunk i at dst + i * pitch and a status word per frame.
 class Decompressor
 {
   public:
     // big_blocks: keep a scratch slot per chunk for frames whose blocks do
     // not fit the LDS budget (kDecodeLdsBytes; c-blosc's own frames).
     // Without it such frames get the status dec::kUnsupported.
-    Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks = true);
-    // device bytes a Decompressor(max_chunk_bytes, max_chunks) allocates
+    // codecs: dec::kFamilyLz4 | dec::kFamilyZstd.  With the zstd family the
+    // scratch slot per chunk is always kept (shuffled blocks and compare
+    // mode are staged there) and a literal slot per (chunk, pass) is added.
+    Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks = true,
+                 uint32_t codecs = dec::kFamilyLz4);
+    // device bytes a Decompressor of these arguments allocates
     static uint64_t scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks,
-                                  bool big_blocks = true);
+                                  bool big_blocks = true, uint32_t codecs = dec::kFamilyLz4);
     // Enqueue on `stream`.  order (device, optional): frame position -> chunk
     // slot of dst.  bad (device, optional, n_chunks words): compare mode --
     // dst is read, not written, and bad[q] = 1 where frame q does not
@@ -234,13 +239,17 @@ class Decompressor
              uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
              uint32_t* status, hipStream_t stream, const uint32_t* order = nullptr,
              uint32_t* bad = nullptr);
-    uint64_t device_bytes() const { return scratch_.n; }
+    uint64_t device_bytes() const { return scratch_.n + zlit_.n; }
+    uint32_t codecs() const { return codecs_; }
 
   private:
     uint64_t max_chunk_bytes_;
     uint32_t max_chunks_;
+    uint32_t codecs_;
     uint64_t scratch_pitch_ = 0;
-    DevBuf scratch_;
+    uint64_t zlit_pitch_ = 0;
+    uint32_t zpasses_ = 0;
+    DevBuf scratch_, zlit_;
 };
 
 struct ArrayDesc
@@ -379,10 +388,16 @@ struct StageLevel
     std::vector<int64_t> comp_layer;       // layer compressed in each slot
     std::vector<int32_t> comp_codec;       // ... and with which codec
     // on-device verification of compressed layers (verify_layer), allocated
-    // by the first verify call: the decoder, per slot the frame statuses
+    // by the first verify call or by verify_prepare: the decoder, per slot the frame statuses
     // and mismatch words ([status n_chunks][bad n_chunks], device and pinned
     // host copy), the event after the read-back and the layer verified
     std::unique_ptr<Decompressor> dec;
+    // verify_prepare(zstd): the level's zstd decoder (one decoded copy of a
+    // layer slot's chunks + literal slots; shared by the slots, whose
+    // verifies run in order on one stream) and a device copy of the offsets
+    // of a layer whose frames were made on the host
+    std::unique_ptr<Decompressor> zdec;
+    DevBuf voffsets;
     std::vector<DevBuf> vwords;
     std::vector<PinnedBuf> h_vwords;
     std::vector<hipEvent_t> verify_ev;
@@ -486,6 +501,9 @@ class Stage
     // that compressed it.  frames == nullptr: the stage's own frames;
     // otherwise a device copy of them (same order, same offsets).
     void verify_layer(uint32_t level, uint64_t layer, const void* frames, size_t frames_bytes);
+    // allocate now what verify_layer needs for layers of these codec
+    // families (dec::kFamily*), on every level split on the device
+    void verify_prepare(uint32_t codecs);
     // waits; chunks that did not verify and the lowest such chunk index
     void verify_result(uint32_t level, uint64_t layer, uint32_t* n_bad, uint32_t* first_bad);
     void finalize();

@@ -37,13 +37,32 @@ enum : uint32_t
 };
 
 constexpr uint32_t kZstdMagic = 0xFD2FB528u;
+constexpr uint32_t kSkippableMagic = 0x184D2A50u; // .. 0x184D2A5F
 constexpr uint32_t kCodecLz4 = 1; // flags >> 5 (LZ4 and LZ4HC share it)
+constexpr uint32_t kCodecZstd = 4;
 constexpr uint32_t kMaxSplit = 16; // a block splits into at most 16 streams
 
 AQZ_HD inline uint32_t
 rd32(const uint8_t* p)
 {
     return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
+}
+
+// Codec families of a decoder (== AQZ_DECODE_CODEC_* of aqz_gpu.h)
+constexpr uint32_t kFamilyLz4 = 1, kFamilyZstd = 2;
+
+// Which decoder a frame belongs to, by its first bytes: kFamilyLz4 a blosc1 frame
+// of the LZ4 codec, kFamilyZstd a plain zstd (or skippable) frame or a blosc1 frame of the zstd codec,
+// 0 anything else.
+AQZ_HD inline uint32_t
+frame_family(const uint8_t* f, uint64_t frame_bytes)
+{
+    if (frame_bytes >= 4 && (rd32(f) == kZstdMagic || (rd32(f) & 0xfffffff0u) == kSkippableMagic))
+        return kFamilyZstd;
+    if (frame_bytes < 16 || f[0] != 2)
+        return 0;
+    const uint32_t c = uint32_t(f[2]) >> 5;
+    return c == kCodecLz4 ? kFamilyLz4 : c == kCodecZstd ? kFamilyZstd : 0u;
 }
 
 struct FrameInfo
@@ -55,9 +74,12 @@ struct FrameInfo
 };
 
 // The 16-byte header of the frame [f, f + frame_bytes) that must decode to
-// chunk_bytes.  kOk, or the status the frame gets.
+// chunk_bytes.  kOk, or the status the frame gets.  codec: the compressor
+// code (flags >> 5) the caller decodes; the zstd decoder (aqz_zstddec.hh)
+// passes kCodecZstd for the same container.
 AQZ_HD inline uint32_t
-parse_header(const uint8_t* f, uint64_t frame_bytes, uint64_t chunk_bytes, FrameInfo& h)
+parse_header(const uint8_t* f, uint64_t frame_bytes, uint64_t chunk_bytes, FrameInfo& h,
+             uint32_t codec = kCodecLz4)
 {
     if (frame_bytes >= 4 && rd32(f) == kZstdMagic)
         return kUnsupported; // a plain zstd frame
@@ -70,7 +92,7 @@ parse_header(const uint8_t* f, uint64_t frame_bytes, uint64_t chunk_bytes, Frame
     h.nbytes = rd32(f + 4);
     h.blocksize = rd32(f + 8);
     h.cbytes = rd32(f + 12);
-    if ((h.flags >> 5) != kCodecLz4)
+    if ((h.flags >> 5) != codec)
         return kUnsupported;
     if (h.typesize == 0 || h.nbytes != chunk_bytes || h.cbytes != frame_bytes)
         return kBadHeader;

@@ -620,7 +620,19 @@ aqz_status aqz_stage_finalize(aqz_stage* st);
  * output would run per chunk is blosc_decompress_ctx.
  * A malformed frame is a per-chunk status, never a fault: reads end at the
  * frame's end, writes at the chunk's end, and the other frames of the run
- * are decoded as if it were not there. */
+ * are decoded as if it were not there.
+ *
+ * The zstd codecs (AQZ_CODEC_BLOSC_ZSTD, AQZ_CODEC_ZSTD) are opt-in, because
+ * their decoder needs device scratch the LZ4 one does not: a decoder made by
+ * aqz_decompressor_create_for with AQZ_DECODE_CODEC_ZSTD also decodes blosc1
+ * frames whose compressor code is zstd (each stream one zstd frame; memcpyed
+ * frames included) and plain zstd frames that decode to exactly chunk_bytes
+ * -- any conforming RFC 8878 frame without a dictionary (this library's and
+ * libzstd's at any level: Single_Segment or windowed, any Frame_Content_Size
+ * width, Raw / RLE / Compressed blocks, all literal kinds and table modes,
+ * repeat offsets, matches across blocks at any distance).  A content checksum
+ * is accounted for (its 4 bytes) and NOT verified.  A frame's kind comes from
+ * its own first bytes, so one run may mix all of them. */
 #define AQZ_DECODE_OK 0          /* the chunk holds the decoded bytes */
 #define AQZ_DECODE_SKIPPED 1     /* zero-length frame: the chunk was zero-filled (an
                                     unwritten chunk reads as fill_value 0, array.cpp:279) */
@@ -628,18 +640,46 @@ aqz_status aqz_stage_finalize(aqz_stage* st);
                                     frame size, blocksize 0 or no multiple of typesize, a
                                     block start outside the frame, or offsets that do not
                                     describe a frame inside frames_bytes */
-#define AQZ_DECODE_CORRUPT 3     /* a stream record or an LZ4 sequence leaves its bounds */
-#define AQZ_DECODE_UNSUPPORTED 4 /* not the LZ4 codec: blosc-zstd frames, plain zstd frames */
+#define AQZ_DECODE_CORRUPT 3     /* a stream record or an LZ4 sequence leaves its bounds; in
+                                    a zstd frame, anything wrong inside the blocks (sizes,
+                                    Huffman / FSE descriptions, bitstreams, sequences,
+                                    offsets, output length) or after the last one */
+#define AQZ_DECODE_UNSUPPORTED 4 /* a codec the decoder was not created for (blosc-zstd and
+                                    plain zstd frames unless AQZ_DECODE_CODEC_ZSTD, blosc-lz4
+                                    frames unless AQZ_DECODE_CODEC_LZ4); always: other blosc
+                                    codecs, a zstd Dictionary_ID other than 0, a skippable
+                                    zstd frame.  (For zstd frames BAD_HEADER covers: a
+                                    stream or plain frame without the zstd magic, a reserved
+                                    frame-header bit, a Frame_Content_Size that differs from
+                                    the expected length, a header that does not fit.) */
+#define AQZ_DECODE_CODEC_LZ4 1u  /* blosc1 frames with the LZ4 codec, memcpyed frames */
+#define AQZ_DECODE_CODEC_ZSTD 2u /* blosc1 frames with the zstd codec, plain zstd frames */
 typedef struct aqz_decompressor aqz_decompressor;
 /* A decoder with device scratch for runs of up to max_chunks frames of up to
- * max_chunk_bytes each (aqz_decompressor_scratch_bytes). */
+ * max_chunk_bytes each (aqz_decompressor_scratch_bytes).  It decodes
+ * AQZ_DECODE_CODEC_LZ4 only. */
 aqz_status aqz_decompressor_create(uint64_t max_chunk_bytes, uint32_t max_chunks,
                                    aqz_decompressor** out);
+/* The same for the codecs listed (AQZ_DECODE_CODEC_* or-ed; 0 or unknown bits:
+ * AQZ_STATUS_INVALID_ARGUMENT).  Zero-length frames are skipped chunks whatever
+ * the codecs. */
+aqz_status aqz_decompressor_create_for(uint64_t max_chunk_bytes, uint32_t max_chunks,
+                                       uint32_t codecs, aqz_decompressor** out);
 void aqz_decompressor_destroy(aqz_decompressor* d);
 /* Device bytes aqz_decompressor_create allocates: one slot per chunk, used by
  * frames whose blocks exceed the on-chip budget (32 KiB; c-blosc's frames of
  * large chunks).  0 on invalid sizes.  No GPU needed. */
 uint64_t aqz_decompressor_scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks);
+/* Device bytes aqz_decompressor_create_for allocates, exactly.  With
+ * AQZ_DECODE_CODEC_ZSTD: the slot per chunk (max_chunk_bytes rounded up to 16;
+ * shuffled blosc blocks and everything in compare mode are decoded there,
+ * since zstd matches reach back farther than any on-chip window) plus the
+ * Huffman-literal slots: min(max_chunk_bytes, 128 KiB) rounded up to 16, times
+ * min(8, ceil(max_chunk_bytes / 32 KiB)) concurrent block decodes per chunk.
+ * Nothing is allocated by aqz_decompressor_run.  0 on invalid arguments.  No
+ * GPU needed. */
+uint64_t aqz_decompressor_scratch_bytes_for(uint64_t max_chunk_bytes, uint32_t max_chunks,
+                                            uint32_t codecs);
 /* Decode n_chunks frames lying back to back at frames (device, frames_bytes
  * in all): frame i is bytes [offsets[i], offsets[i + 1]) -- offsets (device,
  * n_chunks + 1 uint64) as aqz_compressor_run and aqz_stage_compress_layer
@@ -661,12 +701,29 @@ aqz_status aqz_decompressor_run(aqz_decompressor* d, const void* frames, size_t 
  * compression (the stream aqz_stage_compress_layer runs on).  The slot is not reused until
  * the comparison has read it.  The layer must have been compressed with AQZ_CODEC_BLOSC_LZ4
  * (any clevel) and still be resident (else AQZ_STATUS_INVALID_ARGUMENT); layers compressed
- * with a zstd codec return AQZ_STATUS_NOT_YET_IMPLEMENTED.  The first call of a stage
- * allocates the decoder state (two words per chunk and slot, device and pinned; no copy of
- * the layer: the comparison happens as the blocks are un-shuffled), which
- * aqz_stage_memory_usage reports from then on. */
+ * with a zstd codec return AQZ_STATUS_NOT_YET_IMPLEMENTED unless
+ * aqz_stage_verify_prepare was called with AQZ_DECODE_CODEC_ZSTD.  A zstd layer whose
+ * frames were made on the host (AQZ_ZSTD_HOST=1) has no device frames of its own: it is
+ * refused with AQZ_STATUS_INVALID_ARGUMENT unless `frames` is given.  The first LZ4 verify
+ * of a stage allocates the LZ4 decoder state (two words per chunk and slot, device and
+ * pinned; no copy of the layer: the comparison happens as the blocks are un-shuffled),
+ * which aqz_stage_memory_usage reports from then on. */
 aqz_status aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer,
                                   const void* frames, size_t frames_bytes);
+/* Allocate now, for every level the stage splits on the device, the decoder state
+ * aqz_stage_verify_layer needs for layers of the listed codecs (AQZ_DECODE_CODEC_* or-ed;
+ * 0 or unknown bits: AQZ_STATUS_INVALID_ARGUMENT); aqz_stage_memory_usage reports it from
+ * this call on.  With AQZ_DECODE_CODEC_ZSTD that is, per level: the two words per chunk
+ * and slot (device and pinned), and one zstd decoder for a layer slot's chunks
+ * (aqz_decompressor_scratch_bytes_for(chunk bytes, chunks per layer,
+ * AQZ_DECODE_CODEC_ZSTD)) -- one decoded copy of a layer slot's chunks, which the
+ * comparison reads (zstd matches reach back up to the whole frame, so the compare cannot
+ * happen as the blocks are un-shuffled, as it does for LZ4), plus the Huffman-literal
+ * slots.  One decoder serves all slots of a level: verifies of a level run in order on
+ * the hand-off stream.  Without this call nothing changes: zstd layers stay
+ * AQZ_STATUS_NOT_YET_IMPLEMENTED and the first LZ4 verify allocates what it always did.
+ * Calling it again adds the codecs not yet prepared. */
+aqz_status aqz_stage_verify_prepare(aqz_stage* st, uint32_t codecs);
 /* Waits.  *n_bad = chunks whose decoded bytes differ from the resident chunk or whose
  * decode status is an error.  A skipped chunk is good iff the resident chunk is all zero.
  * *first_bad = lowest such chunk index (aqz_chunk_entry.chunk), UINT32_MAX if none. */

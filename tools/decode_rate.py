@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Dev harness (not product): rates of the device blosc1-LZ4 decoder and of
-the stage's on-device verification, next to the device compressor's rate on
-the same data and c-blosc's one-core decode of the same frames on this host.
+"""Dev harness (not product): rates of the device decoders (blosc1-LZ4; with
+--codecs blosc-zstd,zstd also the zstd decoder) and of the stage's on-device
+verification, next to the device compressor's rate on the same data and
+c-blosc's (libzstd's, for plain zstd frames) one-core decode of the same
+frames on this host.
 
 One C2-shaped chunk layer: 512 MiB of camera-like u16 in 64 chunks of
 256x256x64 (8 MiB), lz4 clevel 5, byte shuffle and bitshuffle.  Everything is
@@ -19,6 +21,7 @@ timed in this one process after a warm-up run of each call:
 Rates are GB/s (1e9) of uncompressed bytes.  One JSON line per shuffle mode:
 
   python3 tools/decode_rate.py [--reps 10] [--out profiles/r07_decode_rate.jsonl]
+  python3 tools/decode_rate.py --codecs blosc-zstd,zstd --clevel 3 --out <file>
 """
 import argparse
 import json
@@ -63,7 +66,11 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-chunks", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r07_decode_rate.jsonl"))
+    ap.add_argument("--codecs", default="lz4", help="comma list of lz4, blosc-zstd, zstd")
+    ap.add_argument("--clevel", type=int, default=5)
     args = ap.parse_args()
+    codec_ids = {"lz4": aqz.CODEC_BLOSC_LZ4, "blosc-zstd": aqz.CODEC_BLOSC_ZSTD,
+                 "zstd": aqz.CODEC_ZSTD}
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     src = camera(dev)
@@ -75,15 +82,20 @@ def main():
     except Exception:
         have_blosc = False
     rows = []
-    for shuffle in (1, 2):
-        comp = aqz.Compressor(CHUNK, 2, clevel=5, shuffle=shuffle)
+    cases = [(name, sh) for name in args.codecs.split(",")
+             for sh in ((0,) if name == "zstd" else (1, 2))]
+    for name, shuffle in cases:
+        codec = codec_ids[name]
+        zstd = name != "lz4"
+        comp = aqz.Compressor(CHUNK, 2, codec=codec, clevel=args.clevel, shuffle=shuffle)
         cap = comp.max_bytes(N_CHUNKS)
         frames = torch.empty(cap, dtype=torch.uint8, device=dev)
         off = torch.empty(N_CHUNKS + 1, dtype=torch.int64, device=dev)
         c_ms = timed(lambda: comp.run_ptr(src.data_ptr(), CHUNK, N_CHUNKS, frames.data_ptr(), cap,
                                           off.data_ptr(), stream), args.reps)
         total = int(off[-1].item())
-        dec = aqz.Decompressor(CHUNK, N_CHUNKS)
+        dec = aqz.Decompressor(CHUNK, N_CHUNKS,
+                               codecs=aqz.DECODE_CODEC_ZSTD if zstd else aqz.DECODE_CODEC_LZ4)
         out = torch.empty(layer_bytes, dtype=torch.uint8, device=dev)
         status = torch.empty(N_CHUNKS, dtype=torch.int32, device=dev)
         d_ms = timed(lambda: dec.run_ptr(frames.data_ptr(), cap, off.data_ptr(), N_CHUNKS,
@@ -91,12 +103,26 @@ def main():
                      args.reps)
         exact = bool(torch.equal(out, src)) and not bool(status.any())
         row = {"tool": "tools/decode_rate.py", "layer": "C2 level 0: 64 chunks of 256x256x64 u16",
-               "layer_bytes": layer_bytes, "codec": "blosc-lz4", "clevel": 5, "shuffle": shuffle,
+               "layer_bytes": layer_bytes, "codec": "blosc-" + name if name == "lz4" else name,
+               "clevel": args.clevel, "shuffle": shuffle,
+               "decoder_scratch_bytes": dec.scratch_bytes(),
                "blocksize": comp.blocksize, "compressed_bytes": total,
                "ratio": round(layer_bytes / total, 3), "reps": args.reps,
                "compress_ms": round(c_ms, 3), "compress_gbs": gbs(c_ms),
                "decode_ms": round(d_ms, 3), "decode_gbs": gbs(d_ms), "decode_exact": exact}
-        if have_blosc:
+        if name == "zstd":
+            from codec_helpers import libzstd, zstd_decode
+            if libzstd() is not None:
+                o = off.cpu().numpy()
+                k = min(args.host_chunks, N_CHUNKS)
+                host = [frames[int(o[i]):int(o[i + 1])].cpu().numpy().tobytes() for i in range(k)]
+                zstd_decode(host[0], CHUNK)
+                t0 = time.perf_counter()
+                for fr in host:
+                    zstd_decode(fr, CHUNK)
+                dt = time.perf_counter() - t0
+                row["libzstd_1core_decode_gbs"] = round(k * CHUNK / dt / 1e9, 2)
+        elif have_blosc:
             o = off.cpu().numpy()
             k = min(args.host_chunks, N_CHUNKS)
             host = [frames[int(o[i]):int(o[i + 1])].cpu().numpy().tobytes() for i in range(k)]
@@ -119,7 +145,9 @@ def main():
                        max_batch_frames=PLANES)
         st.append_ptr(src.data_ptr(), PLANES, aqz.MEM_DEVICE)
         st.synchronize()
-        st.compress_layer(0, 0, clevel=5, shuffle=shuffle)
+        if zstd:
+            st.verify_prepare(aqz.DECODE_CODEC_ZSTD)
+        st.compress_layer(0, 0, codec=codec, clevel=args.clevel, shuffle=shuffle)
         st.compressed_offsets(0, 0)
         res = st.verify_layer(0, 0)     # warm-up (allocates the decoder state)
         t0 = time.perf_counter()
