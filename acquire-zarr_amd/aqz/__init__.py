@@ -9,6 +9,8 @@ Mirrors the reference interfaces:
   Downsampler  <- zarr::Downsampler (src/streaming/downsampler.hh:12-64)
   Stage        <- MultiscaleArray::write_frame hot path
                   (src/streaming/multiscale.array.cpp:57-74, 291-325)
+  Reader       <- no counterpart: the inverse of Array::write_frame_to_chunks_
+                  (src/streaming/array.cpp:537-619) and of the chunk codecs
 """
 from __future__ import annotations
 
@@ -137,6 +139,15 @@ class LevelLayoutC(C.Structure):
                 ("frames_per_layer", C.c_uint64), ("frame_bytes", C.c_uint64),
                 ("width", C.c_uint32), ("height", C.c_uint32),
                 ("chunk_pitch", C.c_uint64)]
+
+
+class ReaderDescC(C.Structure):
+    _fields_ = [("dimensions", C.POINTER(Dimension)),
+                ("dimension_count", C.c_size_t),
+                ("data_type", C.c_int32),
+                ("storage_dimension_order", C.POINTER(C.c_size_t)),
+                ("codecs", C.c_uint32), ("max_frames_bytes", C.c_uint64),
+                ("device", C.c_int32)]
 
 
 def build_library(force: bool = False) -> str:
@@ -289,6 +300,15 @@ def lib():
         "aqz_shard_table_bytes": ([u32], sz),
         "aqz_shard_table": ([vp, vp, u32, vp, sz], i32),
         "aqz_crc32c": ([vp, sz], u32),
+        "aqz_shard_table_parse": ([vp, sz, u32, vp, vp, C.POINTER(i32)], i32),
+        "aqz_reader_create": ([C.POINTER(ReaderDescC), C.POINTER(vp)], i32),
+        "aqz_reader_destroy": ([vp], None),
+        "aqz_reader_device_bytes": ([C.POINTER(ReaderDescC)], u64),
+        "aqz_reader_layout": ([vp, C.POINTER(LevelLayoutC)], i32),
+        "aqz_reader_load_frames": ([vp, vp, sz, i32, vp, vp, u32, i32, vp], i32),
+        "aqz_reader_load_chunks": ([vp, vp, u64, vp, u32, vp], i32),
+        "aqz_reader_read_frames": ([vp, u32, u32, vp, u64, vp], i32),
+        "aqz_reader_status": ([vp, vp, sz, C.POINTER(u32)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -769,6 +789,15 @@ class Stage:
                                           MEM_HOST), "copy_layer")
         return out, flags
 
+    def device_layer(self, level, layer):
+        """(chunks ptr, has_data ptr, tag) of a resident layer
+        (aqz_stage_device_layer): chunk c at chunks + c * layout(level)
+        ["chunk_pitch"], with data iff its has_data word equals tag."""
+        chunks, flags = C.c_void_p(), C.c_void_p()
+        _check(lib().aqz_stage_device_layer(self.h, level, layer, C.byref(chunks),
+                                            C.byref(flags)), "device_layer")
+        return chunks.value, flags.value, layer // self.layout(level)["layer_slots"] + 1
+
     def copy_layer_async(self, level, layer, dst_ptr, cap, has_data_ptr=None,
                          has_data_cap=0):
         """Enqueue the D2H hand-off of a resident layer (returns at once)."""
@@ -1021,6 +1050,110 @@ def shard_table(offsets, extents) -> bytes:
 
 def crc32c(data: bytes) -> int:
     return lib().aqz_crc32c(data, len(data))
+
+
+def shard_table_parse(table: bytes, chunks_per_shard: int):
+    """(offsets, extents, crc_ok) of a shard's index table (aqz_shard_table_parse,
+    the inverse of shard_table); UINT64_MAX pairs are chunks never written."""
+    buf = np.frombuffer(bytes(table), dtype=np.uint8)
+    off = np.empty(chunks_per_shard, dtype=np.uint64)
+    ext = np.empty(chunks_per_shard, dtype=np.uint64)
+    ok = C.c_int32(0)
+    _check(lib().aqz_shard_table_parse(buf.ctypes.data, buf.nbytes, chunks_per_shard,
+                                       off.ctypes.data, ext.ctypes.data, C.byref(ok)),
+           "aqz_shard_table_parse")
+    return off, ext, bool(ok.value)
+
+
+def _reader_desc(dims, dtype, storage_order, codecs, max_frames_bytes, device):
+    keep = [_dims_c(dims)]
+    order = None
+    if storage_order is not None:
+        order = (C.c_size_t * len(storage_order))(*storage_order)
+        keep.append(order)
+    return ReaderDescC(keep[0], len(dims), dtype, order, codecs, max_frames_bytes,
+                       device), keep
+
+
+def reader_device_bytes(dims, dtype, storage_order=None, codecs=0, max_frames_bytes=0,
+                        device=0):
+    """Device bytes a Reader of this description allocates, exactly (0 when the
+    description is invalid; no GPU needed)."""
+    d, _keep = _reader_desc(dims, dtype, storage_order, codecs, max_frames_bytes, device)
+    return lib().aqz_reader_device_bytes(C.byref(d))
+
+
+class Reader:
+    """One level's chunk layers back to row-major frames on the device
+    (aqz_reader_*): the layer is loaded from frames of any codec or from
+    decoded chunks resident on the device, then read frame by frame in the
+    order and orientation the frames were appended."""
+
+    def __init__(self, dims, dtype, storage_order=None, codecs=0, max_frames_bytes=0,
+                 device=0):
+        self._desc, self._keep = _reader_desc(dims, dtype, storage_order, codecs,
+                                              max_frames_bytes, device)
+        h = C.c_void_p()
+        _check(lib().aqz_reader_create(C.byref(self._desc), C.byref(h)), "aqz_reader_create")
+        self.h = h
+        self._held = None  # what the loaded layer borrows
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.aqz_reader_destroy(self.h)
+            self.h = None
+            self._held = None
+
+    def __del__(self):
+        self.close()
+
+    def device_bytes(self):
+        return lib().aqz_reader_device_bytes(C.byref(self._desc))
+
+    def layout(self):
+        l = LevelLayoutC()
+        _check(lib().aqz_reader_layout(self.h, C.byref(l)), "aqz_reader_layout")
+        return {f: getattr(l, f) for f, _ in LevelLayoutC._fields_}
+
+    def load_frames(self, frames, offsets, chunk_of_frame=None, codec=CODEC_BLOSC_LZ4,
+                    frames_bytes=None, stream_ptr=None):
+        """frames: numpy array / HostBuffer / torch tensor (or (ptr, mem));
+        offsets: n + 1 frame starts + total; chunk_of_frame None: the order
+        Stage.compress_layer writes."""
+        if isinstance(frames, tuple):
+            p, mem = frames
+        else:
+            p, mem = _ptr(frames)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(off) - 1
+        if frames_bytes is None:
+            frames_bytes = int(off[-1])
+        cof = None
+        if chunk_of_frame is not None:
+            cof = np.ascontiguousarray(chunk_of_frame, dtype=np.uint32)
+            assert len(cof) == n
+        _check(lib().aqz_reader_load_frames(self.h, p, frames_bytes, mem, off.ctypes.data,
+                                            cof.ctypes.data if cof is not None else None, n,
+                                            codec, stream_ptr), "aqz_reader_load_frames")
+        self._held = frames
+
+    def load_chunks(self, chunks_ptr, pitch, has_data_ptr=None, tag=0, stream_ptr=None):
+        _check(lib().aqz_reader_load_chunks(self.h, chunks_ptr, pitch, has_data_ptr, tag,
+                                            stream_ptr), "aqz_reader_load_chunks")
+        self._held = None
+
+    def read_frames_ptr(self, first, count, dst_ptr, dst_stride, stream_ptr=None):
+        _check(lib().aqz_reader_read_frames(self.h, first, count, dst_ptr, dst_stride,
+                                            stream_ptr), "aqz_reader_read_frames")
+
+    def status(self):
+        """(per-chunk DECODE_* by chunk index, n_bad) of the last load; waits."""
+        n = self.layout()["chunks_per_layer"]
+        st = np.empty(n, dtype=np.uint32)
+        bad = C.c_uint32(0)
+        _check(lib().aqz_reader_status(self.h, st.ctypes.data, n, C.byref(bad)),
+               "aqz_reader_status")
+        return st, bad.value
 
 
 class ShardAssembler:

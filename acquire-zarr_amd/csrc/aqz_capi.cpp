@@ -4,6 +4,7 @@
 #include "aqz_gpu_bench.h"
 
 #include "aqz_engine.hh"
+#include "aqz_reader.hh"
 
 #include <cstring>
 #include <new>
@@ -33,6 +34,11 @@ struct aqz_compressor
 struct aqz_decompressor
 {
     std::unique_ptr<Decompressor> d;
+    int32_t sticky = AQZ_STATUS_SUCCESS;
+};
+struct aqz_reader
+{
+    std::unique_ptr<Reader> r;
     int32_t sticky = AQZ_STATUS_SUCCESS;
 };
 
@@ -141,6 +147,35 @@ to_desc(const aqz_array_desc* d)
     if (a.dtype < 0 || a.dtype >= AQZ_DTYPE_COUNT)
         throw Error(AQZ_STATUS_INVALID_ARGUMENT, "Invalid data type");
     return a;
+}
+
+ReaderDesc
+to_reader_desc(const aqz_reader_desc* d)
+{
+    if (!d)
+        throw Error(AQZ_STATUS_INVALID_ARGUMENT, "null desc");
+    ReaderDesc r;
+    r.dims = to_dims(d->dimensions, d->dimension_count);
+    r.dtype = d->data_type;
+    if (r.dtype < 0 || r.dtype >= AQZ_DTYPE_COUNT)
+        throw Error(AQZ_STATUS_INVALID_ARGUMENT, "Invalid data type");
+    if (d->storage_dimension_order)
+        r.storage_order.assign(d->storage_dimension_order,
+                               d->storage_dimension_order + d->dimension_count);
+    r.codecs = d->codecs;
+    r.max_frames_bytes = d->max_frames_bytes;
+    r.device = d->device;
+    return r;
+}
+
+template<typename F>
+aqz_status
+guard_sticky(aqz_reader* o, F&& f)
+{
+    if (!o || !o->r)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    DeviceScope ds(o->r->device());
+    return guard_sticky<aqz_reader>(o, std::forward<F>(f));
 }
 
 void
@@ -1279,4 +1314,119 @@ uint32_t
 aqz_crc32c(const void* data, size_t n)
 {
     return data ? crc32c(static_cast<const uint8_t*>(data), n) : 0;
+}
+
+// Inverse of aqz_shard_table (Shard::write_table_, shard.cpp:145-166).
+aqz_status
+aqz_shard_table_parse(const void* table, size_t nbytes, uint32_t chunks_per_shard,
+                      uint64_t* offsets, uint64_t* extents, int32_t* crc_ok)
+{
+    if (!table || nbytes != aqz_shard_table_bytes(chunks_per_shard)) {
+        t_last_error = "shard table: null, or not chunks_per_shard * 16 + 4 bytes";
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    }
+    const uint8_t* p = static_cast<const uint8_t*>(table);
+    auto rd = [](const uint8_t* q, int n) {
+        uint64_t v = 0;
+        for (int b = 0; b < n; ++b)
+            v |= uint64_t(q[b]) << (8 * b);
+        return v;
+    };
+    for (uint32_t i = 0; i < chunks_per_shard; ++i) {
+        if (offsets)
+            offsets[i] = rd(p + 16 * size_t(i), 8);
+        if (extents)
+            extents[i] = rd(p + 16 * size_t(i) + 8, 8);
+    }
+    const size_t body = size_t(chunks_per_shard) * 16;
+    if (crc_ok)
+        *crc_ok = crc32c(p, body) == uint32_t(rd(p + body, 4)) ? 1 : 0;
+    return AQZ_STATUS_SUCCESS;
+}
+
+// ---- device reader ---------------------------------------------------------
+aqz_status
+aqz_reader_create(const aqz_reader_desc* desc, aqz_reader** out)
+{
+    if (!out)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    *out = nullptr;
+    return guard([&] {
+        const ReaderDesc d = to_reader_desc(desc);
+        DeviceScope ds(d.device); // the caller's current device is kept
+        auto h = std::make_unique<aqz_reader>();
+        h->r = std::make_unique<Reader>(d);
+        *out = h.release();
+    });
+}
+
+void
+aqz_reader_destroy(aqz_reader* r)
+{
+    if (!r)
+        return;
+    if (r->r) {
+        DeviceScope ds(r->r->device());
+        r->r.reset();
+    }
+    delete r;
+}
+
+uint64_t
+aqz_reader_device_bytes(const aqz_reader_desc* desc)
+{
+    uint64_t n = 0;
+    (void)guard([&] { n = Reader::device_bytes_for(to_reader_desc(desc)); });
+    return n;
+}
+
+aqz_status
+aqz_reader_layout(const aqz_reader* r, aqz_level_layout* out)
+{
+    if (!r || !r->r || !out)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    return guard([&] {
+        const LevelLayout l = r->r->layout();
+        *out = aqz_level_layout{ l.bytes_per_chunk, l.chunks_per_layer,
+                                 l.layer_slots,     l.frames_per_layer,
+                                 l.frame_bytes,     l.width,
+                                 l.height,          l.chunk_pitch };
+    });
+}
+
+aqz_status
+aqz_reader_load_frames(aqz_reader* r, const void* frames, size_t frames_bytes, int32_t mem,
+                       const uint64_t* offsets, const uint32_t* chunk_of_frame,
+                       uint32_t n_frames, int32_t codec, void* stream)
+{
+    return guard_sticky(r, [&] {
+        r->r->load_frames(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec,
+                          static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_reader_load_chunks(aqz_reader* r, const void* chunks, uint64_t pitch,
+                       const uint32_t* has_data, uint32_t tag, void* stream)
+{
+    return guard_sticky(r, [&] {
+        r->r->load_chunks(chunks, pitch, has_data, tag, static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_reader_read_frames(aqz_reader* r, uint32_t first, uint32_t count, void* dst,
+                       uint64_t dst_stride, void* stream)
+{
+    return guard_sticky(r, [&] {
+        r->r->read_frames(first, count, dst, dst_stride, static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_reader_status(aqz_reader* r, uint32_t* status, size_t cap, uint32_t* n_bad)
+{
+    if (n_bad)
+        *n_bad = 0;
+    return guard_sticky(r, [&] { r->r->status(status, cap, n_bad); });
 }

@@ -2066,31 +2066,40 @@ shard_table(const uint64_t* offsets, const uint64_t* extents, uint32_t n, uint8_
 // walks shards, array.cpp:777-803; Shard::write_chunk appends each chunk at
 // the shard's running file offset, shard.cpp:55-112).  Without sharding
 // (a shard size of 0) the order is the chunk order.
+bool
+shard_major_order(const ArrayDimensions& ad, std::vector<uint32_t>& order,
+                  std::vector<uint32_t>& shard, std::vector<uint32_t>& internal0)
+{
+    const uint32_t n = ad.number_of_chunks_in_memory();
+    order.resize(n);
+    shard.assign(n, 0);
+    internal0.assign(n, 0);
+    for (uint32_t c = 0; c < n; ++c)
+        order[c] = c;
+    bool sharded = true;
+    for (const Dim& d : ad.dims())
+        sharded = sharded && d.shard_size_chunks > 0;
+    if (!sharded)
+        return false;
+    for (uint32_t c = 0; c < n; ++c) {
+        shard[c] = ad.shard_index_for_chunk(c);
+        internal0[c] = ad.shard_internal_index(c);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return shard[a] != shard[b] ? shard[a] < shard[b] : internal0[a] < internal0[b];
+    });
+    return true;
+}
+
 void
 Stage::build_shard_order(StageLevel& L)
 {
     const uint32_t n = L.n_chunks;
-    L.h_order.resize(n);
-    L.h_shard.assign(n, 0);
-    L.h_internal0.assign(n, 0);
-    for (uint32_t c = 0; c < n; ++c)
-        L.h_order[c] = c;
-    bool sharded = true;
-    for (const Dim& d : L.ad->dims())
-        sharded = sharded && d.shard_size_chunks > 0;
-    if (sharded) {
+    if (shard_major_order(*L.ad, L.h_order, L.h_shard, L.h_internal0)) {
         L.chunks_per_shard = L.ad->chunks_per_shard();
         L.n_shards = L.ad->number_of_shards();
         L.layers_per_shard = std::max<uint32_t>(1, L.ad->chunk_layers_per_shard());
         L.internal_stride = L.chunks_per_shard / L.layers_per_shard;
-        for (uint32_t c = 0; c < n; ++c) {
-            L.h_shard[c] = L.ad->shard_index_for_chunk(c);
-            L.h_internal0[c] = L.ad->shard_internal_index(c);
-        }
-        std::stable_sort(L.h_order.begin(), L.h_order.end(), [&](uint32_t a, uint32_t b) {
-            return L.h_shard[a] != L.h_shard[b] ? L.h_shard[a] < L.h_shard[b]
-                                                : L.h_internal0[a] < L.h_internal0[b];
-        });
     } else {
         L.chunks_per_shard = 1;
         L.n_shards = n;

@@ -439,6 +439,12 @@ uint32_t crc32c(const uint8_t* p, size_t n);
 void shard_table(const uint64_t* offsets, const uint64_t* extents, uint32_t n,
                  uint8_t* out);
 
+// Shard-major order of a level's chunks (position -> chunk) with every chunk's
+// shard and its internal index in the shard's first layer; without sharding
+// (a shard size of 0) the chunk order, and false.
+bool shard_major_order(const ArrayDimensions& ad, std::vector<uint32_t>& order,
+                       std::vector<uint32_t>& shard, std::vector<uint32_t>& internal0);
+
 class Stage
 {
   public:

@@ -1,0 +1,383 @@
+// aqz_reader.cpp -- see aqz_reader.hh.  Citations are to the reference's
+// src/streaming/.
+#include "aqz_reader.hh"
+
+#include <algorithm>
+#include <cstring>
+
+namespace aqz {
+
+namespace {
+
+constexpr int kMemHost = 0, kMemDevice = 1, kMemHostPinned = 2;
+
+uint64_t
+round16(uint64_t n)
+{
+    return (n + 15) & ~uint64_t(15);
+}
+
+// dec::kFamily* a Compression::codec value needs (0: none; ~0u: no such codec)
+uint32_t
+family_of(int32_t codec)
+{
+    switch (codec) {
+        case 0: return 0;
+        case 1: return dec::kFamilyLz4;
+        case 2:
+        case 3: return dec::kFamilyZstd;
+        default: return ~0u;
+    }
+}
+
+} // namespace
+
+struct Reader::Sizes
+{
+    uint32_t F = 0, n = 0;
+    uint64_t tables = 0, words = 0, layer_pitch = 0, layer = 0, staging = 0, decoder = 0;
+};
+
+Reader::Sizes
+Reader::sizes(const ReaderDesc& d, const ArrayDimensions& ad)
+{
+    if (d.codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd))
+        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD, or 0");
+    Sizes s;
+    const uint64_t F = ad.frames_per_chunk_layer();
+    if (F == 0 || F > 0x7fffffffull)
+        throw Error(9, "unsupported frames per chunk layer");
+    const uint64_t bpc = ad.bytes_per_chunk();
+    if (bpc == 0 || bpc > 0x7fffffefull)
+        throw Error(9, "chunk size outside the blosc1 limits");
+    const uint64_t tile_row = uint64_t(ad.width_dim().chunk_size_px) * bytes_of_type(d.dtype);
+    if (tile_row * unsplit::kSlabRows > 0xffffffffull)
+        throw Error(9, "tile rows too long");
+    if (ad.width_dim().array_size_px == 0 || ad.height_dim().array_size_px == 0)
+        throw Error(9, "frame dimensions must be bounded");
+    s.F = uint32_t(F);
+    s.n = ad.number_of_chunks_in_memory();
+    if (s.n == 0)
+        throw Error(9, "no chunks");
+    s.words = uint64_t(s.n) * 8 + (uint64_t(s.n) + 1) * 8 + uint64_t(s.n) * 4 * 2;
+    s.tables = uint64_t(s.F) * 12 + s.words;
+    if (d.codecs) {
+        s.layer_pitch = round16(bpc);
+        s.layer = s.layer_pitch * s.n;
+        s.decoder = Decompressor::scratch_bytes(bpc, s.n, true, d.codecs);
+    }
+    s.staging = d.max_frames_bytes ? d.max_frames_bytes : Compressor::max_bytes(bpc, s.n);
+    return s;
+}
+
+uint64_t
+Reader::device_bytes_for(const ReaderDesc& d)
+{
+    try {
+        const ArrayDimensions ad(d.dims, d.dtype, d.storage_order);
+        const Sizes s = sizes(d, ad);
+        return s.tables + s.layer + s.staging + s.decoder;
+    } catch (const std::exception&) {
+        return 0;
+    }
+}
+
+Reader::Reader(const ReaderDesc& d)
+  : device_(d.device)
+  , codecs_(d.codecs)
+{
+    ad_ = std::make_unique<ArrayDimensions>(d.dims, d.dtype, d.storage_order);
+    const Sizes s = sizes(d, *ad_);
+    g_.W = ad_->width_dim().array_size_px;
+    g_.H = ad_->height_dim().array_size_px;
+    g_.tw = ad_->width_dim().chunk_size_px;
+    g_.th = ad_->height_dim().chunk_size_px;
+    g_.ntx = parts_along(g_.W, g_.tw);
+    g_.nty = parts_along(g_.H, g_.th);
+    g_.bpp = uint32_t(bytes_of_type(d.dtype));
+    g_.n_chunks = s.n;
+    g_.n_frames = s.F;
+    g_.xy = ad_->needs_xy_transposition() ? 1 : 0;
+    g_.bpc = ad_->bytes_per_chunk();
+
+    // the stage's per-frame tables (aqz_engine.cpp, Stage::Stage), with the
+    // chunk's own offset instead of a ring pitch folded in
+    std::vector<uint64_t> tab_off(s.F);
+    std::vector<uint32_t> tab_grp(s.F);
+    for (uint32_t f = 0; f < s.F; ++f) {
+        const uint64_t sf = ad_->transpose_frame_id(f);
+        tab_grp[f] = ad_->tile_group_offset(sf);
+        tab_off[f] = ad_->chunk_internal_offset(sf);
+    }
+    {
+        std::vector<uint32_t> shard, internal0;
+        shard_major_order(*ad_, shard_order_, shard, internal0);
+    }
+    chunk_status_.assign(s.n, dec::kSkipped);
+
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    tables_.alloc(s.tables);
+    uint8_t* q = tables_.p;
+    d_tab_off_ = reinterpret_cast<uint64_t*>(q);
+    q += size_t(s.F) * 8;
+    d_chunk_src_ = reinterpret_cast<uint64_t*>(q);
+    q += size_t(s.n) * 8;
+    d_offsets_ = reinterpret_cast<uint64_t*>(q);
+    q += (size_t(s.n) + 1) * 8;
+    d_tab_grp_ = reinterpret_cast<uint32_t*>(q);
+    q += size_t(s.F) * 4;
+    d_order_ = reinterpret_cast<uint32_t*>(q);
+    q += size_t(s.n) * 4;
+    d_status_ = reinterpret_cast<uint32_t*>(q);
+    hip_check(hipMemcpy(d_tab_off_, tab_off.data(), size_t(s.F) * 8, hipMemcpyHostToDevice),
+              "hipMemcpy");
+    hip_check(hipMemcpy(d_tab_grp_, tab_grp.data(), size_t(s.F) * 4, hipMemcpyHostToDevice),
+              "hipMemcpy");
+    h_words_.alloc(s.words);
+    uint8_t* h = h_words_.p;
+    h_chunk_src_ = reinterpret_cast<uint64_t*>(h);
+    h += size_t(s.n) * 8;
+    h_offsets_ = reinterpret_cast<uint64_t*>(h);
+    h += (size_t(s.n) + 1) * 8;
+    h_order_ = reinterpret_cast<uint32_t*>(h);
+    h += size_t(s.n) * 4;
+    h_status_ = reinterpret_cast<uint32_t*>(h);
+    if (codecs_) {
+        layer_pitch_ = s.layer_pitch;
+        layer_.alloc(s.layer);
+        dec_ = std::make_unique<Decompressor>(g_.bpc, s.n, true, codecs_);
+    }
+    staging_.alloc(s.staging);
+    hip_check(hipEventCreateWithFlags(&load_ev_, hipEventDisableTiming), "hipEventCreate");
+    hip_check(hipEventCreateWithFlags(&read_ev_, hipEventDisableTiming), "hipEventCreate");
+}
+
+Reader::~Reader()
+{
+    // a borrowed source or destination may still be in use by enqueued work
+    if (load_ev_) {
+        (void)hipEventSynchronize(load_ev_);
+        (void)hipEventDestroy(load_ev_);
+    }
+    if (read_ev_) {
+        (void)hipEventSynchronize(read_ev_);
+        (void)hipEventDestroy(read_ev_);
+    }
+    (void)hipGetLastError();
+}
+
+uint64_t
+Reader::device_bytes() const
+{
+    return tables_.n + layer_.n + staging_.n + (dec_ ? dec_->device_bytes() : 0);
+}
+
+LevelLayout
+Reader::layout() const
+{
+    LevelLayout l{};
+    l.bytes_per_chunk = g_.bpc;
+    l.chunks_per_layer = g_.n_chunks;
+    l.layer_slots = 1;
+    l.frames_per_layer = g_.n_frames;
+    l.frame_bytes = unsplit::frame_bytes(g_);
+    // of the frames handed back: acquisition orientation
+    l.width = g_.xy ? g_.H : g_.W;
+    l.height = g_.xy ? g_.W : g_.H;
+    l.chunk_pitch = layer_pitch_ ? layer_pitch_ : g_.bpc;
+    return l;
+}
+
+// The pinned words and the layer buffer are about to be rewritten: the
+// previous load's copies have to be done (host side), and the reads of the
+// previous layer enqueued so far have to run first (device side).
+void
+Reader::begin_load(hipStream_t stream)
+{
+    if (loaded_ != Loaded::None)
+        hip_check(hipEventSynchronize(load_ev_), "hipEventSynchronize");
+    if (read_pending_)
+        hip_check(hipStreamWaitEvent(stream, read_ev_, 0), "hipStreamWaitEvent");
+    loaded_ = Loaded::None;
+}
+
+void
+Reader::load_frames(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
+                    const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
+                    hipStream_t stream)
+{
+    const uint32_t n = g_.n_chunks;
+    const uint32_t fam = family_of(codec);
+    if (fam == ~0u)
+        throw Error(1, "unknown codec");
+    if (fam && !(codecs_ & fam))
+        throw Error(1, "the reader was not created for this codec");
+    if (!offsets || (!frames && frames_bytes))
+        throw Error(1, "null frames or offsets");
+    if (mem != kMemHost && mem != kMemDevice && mem != kMemHostPinned)
+        throw Error(1, "mem: AQZ_MEM_HOST, AQZ_MEM_HOST_PINNED or AQZ_MEM_DEVICE");
+    if (n_frames > n)
+        throw Error(1, "more frames than chunks per layer");
+    if (!chunk_of_frame && n_frames != n)
+        throw Error(1, "without chunk_of_frame every chunk of the layer has a frame");
+    if (offsets[0] > frames_bytes)
+        throw Error(1, "offsets exceed frames_bytes");
+    for (uint32_t q = 0; q < n_frames; ++q)
+        if (offsets[q + 1] < offsets[q] || offsets[q + 1] > frames_bytes)
+            throw Error(1, "offsets are not monotonic or exceed frames_bytes");
+    const uint32_t* order = chunk_of_frame ? chunk_of_frame : shard_order_.data();
+    std::vector<uint8_t> seen(n, 0);
+    for (uint32_t q = 0; q < n_frames; ++q) {
+        if (order[q] >= n)
+            throw Error(1, "chunk_of_frame entry outside the layer");
+        if (seen[order[q]])
+            throw Error(1, "chunk_of_frame lists a chunk twice");
+        seen[order[q]] = 1;
+    }
+    if (mem != kMemDevice && frames_bytes > staging_.n)
+        throw Error(1, "frames_bytes above the reader's max_frames_bytes");
+
+    begin_load(stream);
+    const uint8_t* dframes = static_cast<const uint8_t*>(frames);
+    if (mem != kMemDevice) {
+        if (frames_bytes)
+            hip_check(hipMemcpyAsync(staging_.p, frames, frames_bytes, hipMemcpyHostToDevice,
+                                     stream),
+                      "hipMemcpyAsync");
+        dframes = staging_.p;
+    }
+    for (uint32_t c = 0; c < n; ++c)
+        h_chunk_src_[c] = unsplit::kNoChunk;
+    std::fill(chunk_status_.begin(), chunk_status_.end(), uint32_t(dec::kSkipped));
+    uint64_t align = 0;
+    for (uint32_t q = 0; q < n_frames; ++q) {
+        const uint64_t len = offsets[q + 1] - offsets[q];
+        const uint32_t c = order[q];
+        h_offsets_[q] = offsets[q];
+        h_order_[q] = c;
+        if (len == 0)
+            continue;
+        if (fam) {
+            h_chunk_src_[c] = c * layer_pitch_;
+        } else if (len == g_.bpc) {
+            // a stored chunk is its own frame
+            h_chunk_src_[c] = offsets[q];
+            align |= offsets[q];
+            chunk_status_[c] = dec::kOk;
+        } else {
+            chunk_status_[c] = dec::kBadHeader;
+        }
+    }
+    // the decoder takes a permutation of the layer's chunks (a slot per frame
+    // of the run): the chunks not listed follow as zero-length frames
+    uint32_t fill = n_frames;
+    for (uint32_t c = 0; c < n && fill < n; ++c)
+        if (!seen[c]) {
+            h_offsets_[fill] = offsets[n_frames];
+            h_order_[fill++] = c;
+        }
+    h_offsets_[n] = offsets[n_frames];
+    // [chunk_src][offsets] lie back to back on both sides
+    hip_check(hipMemcpyAsync(d_chunk_src_, h_chunk_src_, size_t(n) * 8 + (size_t(n) + 1) * 8,
+                             hipMemcpyHostToDevice, stream),
+              "hipMemcpyAsync");
+    if (fam) {
+        hip_check(hipMemcpyAsync(d_order_, h_order_, size_t(n) * 4, hipMemcpyHostToDevice,
+                                 stream),
+                  "hipMemcpyAsync");
+        dec_->run(dframes, frames_bytes, d_offsets_, n, layer_.p, layer_pitch_, g_.bpc,
+                  d_status_, stream, d_order_);
+        hip_check(hipMemcpyAsync(h_status_, d_status_, size_t(n) * 4, hipMemcpyDeviceToHost,
+                                 stream),
+                  "hipMemcpyAsync");
+        src_ = layer_.p;
+        src_align_ = uint64_t(reinterpret_cast<uintptr_t>(layer_.p)) | layer_pitch_;
+    } else {
+        src_ = dframes;
+        src_align_ = uint64_t(reinterpret_cast<uintptr_t>(dframes)) | align;
+    }
+    hip_check(hipEventRecord(load_ev_, stream), "hipEventRecord");
+    loaded_frames_ = n;
+    loaded_ = fam ? Loaded::Decoded : Loaded::Raw;
+}
+
+void
+Reader::load_chunks(const void* chunks, uint64_t pitch, const uint32_t* has_data, uint32_t tag,
+                    hipStream_t stream)
+{
+    if (!chunks)
+        throw Error(1, "null chunks");
+    if (pitch < g_.bpc)
+        throw Error(1, "chunk pitch below bytes_per_chunk");
+    begin_load(stream);
+    hip_check(launch_chunk_table(d_chunk_src_, g_.n_chunks, pitch, has_data, tag, stream),
+              "chunk table launch");
+    hip_check(hipMemcpyAsync(h_chunk_src_, d_chunk_src_, size_t(g_.n_chunks) * 8,
+                             hipMemcpyDeviceToHost, stream),
+              "hipMemcpyAsync");
+    hip_check(hipEventRecord(load_ev_, stream), "hipEventRecord");
+    src_ = static_cast<const uint8_t*>(chunks);
+    src_align_ = uint64_t(reinterpret_cast<uintptr_t>(chunks)) | pitch;
+    loaded_ = Loaded::Chunks;
+}
+
+void
+Reader::read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stride,
+                    hipStream_t stream)
+{
+    if (loaded_ == Loaded::None)
+        throw Error(1, "no layer loaded");
+    if (uint64_t(first) + count > g_.n_frames)
+        throw Error(1, "frame range outside the layer");
+    if (count == 0)
+        return;
+    if (!dst)
+        throw Error(1, "null destination");
+    if (dst_stride < unsplit::frame_bytes(g_))
+        throw Error(1, "dst_stride below the frame size");
+    unsplit::Params p{};
+    p.g = g_;
+    p.src = src_;
+    p.chunk_src = d_chunk_src_;
+    p.tab_grp = d_tab_grp_;
+    p.tab_off = d_tab_off_;
+    p.dst = static_cast<uint8_t*>(dst);
+    p.dst_stride = dst_stride;
+    p.first = first;
+    p.count = count;
+    // the load may have been enqueued on another stream
+    hip_check(hipStreamWaitEvent(stream, load_ev_, 0), "hipStreamWaitEvent");
+    const uint64_t align = src_align_ | uint64_t(reinterpret_cast<uintptr_t>(dst)) | dst_stride;
+    hip_check(launch_unsplit(p, align, stream), "unsplit launch");
+    hip_check(hipEventRecord(read_ev_, stream), "hipEventRecord");
+    read_pending_ = true;
+}
+
+void
+Reader::status(uint32_t* status, size_t cap, uint32_t* n_bad)
+{
+    if (loaded_ == Loaded::None)
+        throw Error(1, "no layer loaded");
+    const uint32_t n = g_.n_chunks;
+    if (status && cap < n)
+        throw Error(2, "status array below chunks_per_layer");
+    hip_check(hipEventSynchronize(load_ev_), "hipEventSynchronize");
+    if (loaded_ == Loaded::Decoded) {
+        std::fill(chunk_status_.begin(), chunk_status_.end(), uint32_t(dec::kSkipped));
+        for (uint32_t q = 0; q < loaded_frames_; ++q)
+            chunk_status_[h_order_[q]] = h_status_[q];
+    } else if (loaded_ == Loaded::Chunks) {
+        for (uint32_t c = 0; c < n; ++c)
+            chunk_status_[c] = h_chunk_src_[c] == unsplit::kNoChunk ? dec::kSkipped : dec::kOk;
+    }
+    uint32_t bad = 0;
+    for (uint32_t c = 0; c < n; ++c) {
+        if (status)
+            status[c] = chunk_status_[c];
+        bad += chunk_status_[c] > dec::kSkipped;
+    }
+    if (n_bad)
+        *n_bad = bad;
+}
+
+} // namespace aqz

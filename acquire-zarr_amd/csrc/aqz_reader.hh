@@ -1,0 +1,102 @@
+// aqz_reader.hh -- the device reader: one level's chunk layers back to
+// row-major frames in device memory.
+//
+//   Reader <- the inverse of zarr::Array::write_frame_to_chunks_
+//             (src/streaming/array.cpp:537-619) and, through the device
+//             decoders, of Array::compress_and_flush_data_ (array.cpp:
+//             777-803).  The reference has no read path.
+#pragma once
+
+#include "aqz_engine.hh"
+#include "aqz_unsplit.hh"
+
+namespace aqz {
+
+// aqz_unsplit.hip.  align: see unsplit::copy_unit.
+hipError_t launch_unsplit(const unsplit::Params& p, uint64_t align, hipStream_t stream);
+hipError_t launch_chunk_table(uint64_t* chunk_src, uint32_t n, uint64_t pitch,
+                              const uint32_t* has_data, uint32_t tag, hipStream_t stream);
+
+struct ReaderDesc
+{
+    std::vector<Dim> dims; // of this level, acquisition order
+    int32_t dtype = 0;
+    std::vector<size_t> storage_order; // level 0 only
+    uint32_t codecs = 0;               // dec::kFamily*; 0 = raw chunks only
+    uint64_t max_frames_bytes = 0;     // 0 = Compressor::max_bytes of a layer
+    int32_t device = 0;
+};
+
+class Reader
+{
+  public:
+    explicit Reader(const ReaderDesc& d);
+    ~Reader();
+    Reader(const Reader&) = delete;
+    Reader& operator=(const Reader&) = delete;
+
+    // device bytes Reader(d) allocates, exactly; 0 for an invalid description.
+    // Needs no GPU.
+    static uint64_t device_bytes_for(const ReaderDesc& d);
+    uint64_t device_bytes() const;
+    LevelLayout layout() const;
+    int device() const { return device_; }
+
+    // codec: 0 none, 1 blosc-lz4, 2 blosc-zstd, 3 zstd (Compression::codec)
+    void load_frames(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
+                     const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
+                     hipStream_t stream);
+    void load_chunks(const void* chunks, uint64_t pitch, const uint32_t* has_data, uint32_t tag,
+                     hipStream_t stream);
+    void read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stride,
+                     hipStream_t stream);
+    // waits for the last load; status[c] of chunk c, *n_bad = error statuses
+    void status(uint32_t* status, size_t cap, uint32_t* n_bad);
+
+  private:
+    struct Sizes;
+    static Sizes sizes(const ReaderDesc& d, const ArrayDimensions& ad);
+    void begin_load(hipStream_t stream);
+
+    int32_t device_;
+    uint32_t codecs_;
+    std::unique_ptr<ArrayDimensions> ad_;
+    unsplit::Geom g_{};
+    std::vector<uint32_t> shard_order_; // position -> chunk, as compress_layer writes
+    // one device block: [tab_off F u64][chunk_src n u64][offsets n+1 u64]
+    // [tab_grp F u32][order n u32][status n u32]
+    DevBuf tables_;
+    uint64_t* d_tab_off_ = nullptr;
+    uint64_t* d_chunk_src_ = nullptr;
+    uint64_t* d_offsets_ = nullptr;
+    uint32_t* d_tab_grp_ = nullptr;
+    uint32_t* d_order_ = nullptr;
+    uint32_t* d_status_ = nullptr;
+    // pinned mirror of the per-load part: [chunk_src n][offsets n+1][order n][status n]
+    PinnedBuf h_words_;
+    uint64_t* h_chunk_src_ = nullptr;
+    uint64_t* h_offsets_ = nullptr;
+    uint32_t* h_order_ = nullptr;
+    uint32_t* h_status_ = nullptr;
+    DevBuf layer_;  // decoded chunks at layer_pitch_ (codecs != 0)
+    uint64_t layer_pitch_ = 0;
+    DevBuf staging_; // frames that arrive from host memory
+    std::unique_ptr<Decompressor> dec_;
+    // the loaded layer
+    enum class Loaded
+    {
+        None,
+        Decoded, // status words come from the decoder, by frame position
+        Raw,     // status words were set on the host, by chunk
+        Chunks   // chunk_src was made on the device and copied back
+    } loaded_ = Loaded::None;
+    uint32_t loaded_frames_ = 0;
+    const uint8_t* src_ = nullptr;
+    uint64_t src_align_ = 0;
+    std::vector<uint32_t> chunk_status_;
+    hipEvent_t load_ev_ = nullptr; // the last load has run
+    hipEvent_t read_ev_ = nullptr; // the last read has run
+    bool read_pending_ = false;
+};
+
+} // namespace aqz

@@ -1,0 +1,210 @@
+// aqz_unsplit.hh -- the address map of the device reader's un-split kernel
+// (aqz_unsplit.hip), compiled for host and device from this one text: which
+// bytes of which chunk are which bytes of a row-major frame, with every bound
+// it enforces.  It is the inverse of Array::write_frame_to_chunks_
+// (array.cpp:537-619) with Chunk::write_tile_rows (chunk.cpp:17-58) -- the
+// tile stores of the fused kernels and of aqz_hostsplit.cpp -- and, for the
+// XY-transposed storage order, of transpose_frame (array.cpp:488-534).
+// Only the byte movers differ (the Mover argument of unsplit_item): a serial
+// loop on the host (tests/sanitize/unsplit_sanitize.cpp runs this text under
+// a host sanitizer), the 256 threads of a workgroup on the device.
+//
+// The map.  Frame f of a layer (layer-local id, acquisition order) has the
+// storage id s = transpose_frame_id(f); tab_grp[f] = tile_group_offset(s) and
+// tab_off[f] = chunk_internal_offset(s), the tables of the stage.  Tile
+// (ty, tx) of the frame lies in chunk tab_grp[f] + ty * ntx + tx; row r of
+// the tile starts at tab_off[f] + r * tw * bpp inside the chunk and carries
+// min(tw, W - tx * tw) valid pixels; rows >= H - ty * th do not exist, and
+// the ragged padding of a chunk is never read.  With the XY-transposed
+// storage order, storage pixel (y, x) is acquisition pixel (x, y): the frame
+// handed back has W rows of H pixels.
+#pragma once
+
+#include <cstdint>
+
+#ifndef AQZ_HD
+#if defined(__HIP__) || defined(__CUDACC__)
+#define AQZ_HD __host__ __device__
+#else
+#define AQZ_HD
+#endif
+#endif
+
+namespace aqz {
+namespace unsplit {
+
+// chunk_src entry of a chunk that was never written: its pixels read as
+// zeros (fill_value 0, array.cpp:279)
+constexpr uint64_t kNoChunk = ~uint64_t(0);
+
+// rows of a tile one work item moves (also the edge of the LDS transpose tile)
+constexpr uint32_t kSlabRows = 64;
+
+enum : uint32_t
+{
+    kEmpty = 0, // the item holds no pixel (rows past the frame's last row)
+    kMove = 1,  // the rectangle was handed to the mover
+    kBad = 2,   // geometry and tables disagree: nothing was moved
+};
+
+struct Geom
+{
+    uint32_t W, H;     // storage frame: pixels per row, rows
+    uint32_t tw, th;   // tile (chunk) pixels per row, rows
+    uint32_t ntx, nty; // tiles per frame
+    uint32_t bpp;      // bytes per pixel
+    uint32_t n_chunks; // chunks per layer
+    uint32_t n_frames; // frames per layer
+    uint32_t xy;       // 1: the storage order swaps y and x
+    uint64_t bpc;      // bytes per chunk
+};
+
+AQZ_HD inline uint32_t
+slabs_per_tile(const Geom& g)
+{
+    return (g.th + kSlabRows - 1) / kSlabRows;
+}
+
+// work items of one frame: (ty, tx, slab) with the slab fastest
+AQZ_HD inline uint64_t
+items_per_frame(const Geom& g)
+{
+    return uint64_t(g.ntx) * g.nty * slabs_per_tile(g);
+}
+
+AQZ_HD inline uint64_t
+frame_bytes(const Geom& g)
+{
+    return uint64_t(g.W) * g.H * g.bpp;
+}
+
+// One rectangle of pixels: `rows` rows of `cols` storage pixels inside a
+// chunk, and where they go inside the destination frame.
+struct Rect
+{
+    uint32_t chunk;         // of the layer
+    uint32_t rows, cols;    // storage rows (<= kSlabRows) and pixels per row
+    uint64_t src;           // first byte, inside the chunk
+    uint64_t src_pitch;     // bytes from row to row inside the chunk
+    uint64_t dst;           // first byte, inside the destination frame
+    uint64_t dst_pitch;     // bytes from destination row to destination row
+    uint32_t dst_rows;      // rows (xy: cols) ...
+    uint64_t dst_row_bytes; // ... of cols * bpp (xy: rows * bpp) bytes
+};
+
+// The rectangle of slab `slab` of tile (ty, tx) of a frame whose tile 0 lies
+// in chunk `grp` at byte `internal`.  kMove only when every source byte lies
+// inside [0, bpc) of a chunk below n_chunks and every destination byte inside
+// [0, W * H * bpp).
+AQZ_HD inline uint32_t
+tile_rect(const Geom& g, uint32_t grp, uint64_t internal, uint32_t ty, uint32_t tx,
+          uint32_t slab, Rect& r)
+{
+    if (ty >= g.nty || tx >= g.ntx || g.bpp == 0 || g.tw == 0 || g.th == 0)
+        return kBad;
+    const uint64_t r0 = uint64_t(slab) * kSlabRows; // first row, inside the tile
+    const uint64_t y0 = uint64_t(ty) * g.th + r0;   // ... and inside the frame
+    const uint64_t x0 = uint64_t(tx) * g.tw;
+    if (x0 >= g.W)
+        return kBad;
+    if (r0 >= g.th || y0 >= g.H)
+        return kEmpty;
+    uint64_t rows = g.th - r0;
+    if (rows > kSlabRows)
+        rows = kSlabRows;
+    if (rows > g.H - y0)
+        rows = g.H - y0;
+    uint64_t cols = g.W - x0;
+    if (cols > g.tw)
+        cols = g.tw;
+    const uint64_t chunk = uint64_t(grp) + uint64_t(ty) * g.ntx + tx;
+    if (chunk >= g.n_chunks)
+        return kBad;
+    r.chunk = uint32_t(chunk);
+    r.rows = uint32_t(rows);
+    r.cols = uint32_t(cols);
+    r.src_pitch = uint64_t(g.tw) * g.bpp;
+    r.src = internal + r0 * r.src_pitch;
+    if (r.src + (rows - 1) * r.src_pitch + cols * g.bpp > g.bpc)
+        return kBad;
+    if (!g.xy) {
+        r.dst_pitch = uint64_t(g.W) * g.bpp;
+        r.dst = y0 * r.dst_pitch + x0 * g.bpp;
+        r.dst_rows = r.rows;
+        r.dst_row_bytes = cols * g.bpp;
+    } else {
+        // storage pixel (y, x) -> row x, pixel y of a frame of W rows of H
+        r.dst_pitch = uint64_t(g.H) * g.bpp;
+        r.dst = x0 * r.dst_pitch + y0 * g.bpp;
+        r.dst_rows = r.cols;
+        r.dst_row_bytes = rows * g.bpp;
+    }
+    if (r.dst + (uint64_t(r.dst_rows) - 1) * r.dst_pitch + r.dst_row_bytes > frame_bytes(g))
+        return kBad;
+    return kMove;
+}
+
+// Work item `item` (< items_per_frame) of layer-local frame `frame`: its
+// rectangle goes to the mover -- copy(base, r) (XY: transpose(base, r)) for a
+// chunk at byte `base` of the source, zero(r) for a chunk never written.
+// The mover holds the source and the destination frame; the rectangle it
+// gets is inside both.
+template<bool XY, class Mover>
+AQZ_HD inline uint32_t
+unsplit_item(const Geom& g, const uint32_t* tab_grp, const uint64_t* tab_off,
+             const uint64_t* chunk_src, uint32_t frame, uint64_t item, Mover& m)
+{
+    if (frame >= g.n_frames || item >= items_per_frame(g) || XY != (g.xy != 0))
+        return kBad;
+    const uint32_t spt = slabs_per_tile(g);
+    const uint32_t slab = uint32_t(item % spt);
+    const uint64_t t = item / spt;
+    const uint32_t ty = uint32_t(t / g.ntx), tx = uint32_t(t % g.ntx);
+    Rect r;
+    const uint32_t st = tile_rect(g, tab_grp[frame], tab_off[frame], ty, tx, slab, r);
+    if (st != kMove)
+        return st;
+    const uint64_t base = chunk_src[r.chunk];
+    if (base == kNoChunk)
+        m.zero(r);
+    else if constexpr (XY)
+        m.transpose(base, r);
+    else
+        m.copy(base, r);
+    return kMove;
+}
+
+// Bytes the copy path may move at a time: the largest power of two up to 16
+// that divides every row start and row length on both sides.  `align` is
+// the OR of the source address, every chunk_src entry (or the chunk pitch),
+// the destination address and the destination stride; chunk-internal
+// offsets are multiples of tw * bpp.
+inline uint32_t
+copy_unit(const Geom& g, uint64_t align)
+{
+    const uint64_t a = align | uint64_t(g.tw) * g.bpp | uint64_t(g.W) * g.bpp | 16u;
+    return uint32_t(a & (~a + 1));
+}
+
+// XY path: may pixels be moved as words of bpp bytes?
+inline bool
+pixel_aligned(const Geom& g, uint64_t align)
+{
+    return g.bpp != 0 && (align & (g.bpp - 1)) == 0;
+}
+
+// One launch: frames [first, first + count) of the layer -> dst + i * dst_stride
+struct Params
+{
+    Geom g;
+    const uint8_t* src;        // chunk c at src + chunk_src[c]
+    const uint64_t* chunk_src; // [n_chunks] byte offsets, kNoChunk = never written
+    const uint32_t* tab_grp;   // [n_frames]
+    const uint64_t* tab_off;   // [n_frames]
+    uint8_t* dst;
+    uint64_t dst_stride;       // >= frame_bytes(g)
+    uint32_t first, count;
+};
+
+} // namespace unsplit
+} // namespace aqz

@@ -730,6 +730,101 @@ aqz_status aqz_stage_verify_prepare(aqz_stage* st, uint32_t codecs);
 aqz_status aqz_stage_verify_result(aqz_stage* st, uint32_t level, uint64_t layer,
                                    uint32_t* n_bad, uint32_t* first_bad);
 
+/* ---- device reader: chunk layers and shards back to frames ------------------
+ * The reference has no read path; these are the inverses of its write path.
+ *
+ * Inverse of aqz_shard_table (Shard::write_table_, shard.cpp:145-166); host
+ * only.  table: the nbytes == aqz_shard_table_bytes(chunks_per_shard) bytes at
+ * the end of a shard (else AQZ_STATUS_INVALID_ARGUMENT).  offsets / extents
+ * (chunks_per_shard each; either may be NULL) get the little-endian pairs,
+ * UINT64_MAX pairs for chunks never written; *crc_ok (may be NULL) = the
+ * stored CRC-32C matches the table bytes.  A table whose CRC does not match is
+ * still parsed. */
+aqz_status aqz_shard_table_parse(const void* table, size_t nbytes, uint32_t chunks_per_shard,
+                                 uint64_t* offsets, uint64_t* extents, int32_t* crc_ok);
+
+/* A reader serves one array, i.e. one level: it turns a chunk layer of that
+ * level -- raw, compressed with any AQZ_CODEC_*, or gathered from shard files
+ * -- into row-major frames in device memory, in the order and orientation
+ * the frames were appended (the inverse of Array::write_frame_to_chunks_,
+ * array.cpp:537-619, of transpose_frame_id and of transpose_frame,
+ * array.cpp:488-534).  Chunks never written read as zeros (fill_value 0,
+ * array.cpp:279).  Levels >= 1 are stored in storage order throughout: a
+ * reader for one takes that level's dims (aqz_stage_level_dims) and no
+ * storage order. */
+typedef struct aqz_reader aqz_reader;
+typedef struct
+{
+    const aqz_dimension* dimensions; /* of this level, acquisition order */
+    size_t dimension_count;
+    int32_t data_type;               /* AQZ_DTYPE_* */
+    const size_t* storage_dimension_order; /* level 0 only; NULL = acquisition order */
+    uint32_t codecs;           /* AQZ_DECODE_CODEC_* or-ed; 0 = raw chunks only */
+    uint64_t max_frames_bytes; /* device staging for frames given in host memory;
+                                  0 = aqz_compressor_max_bytes(bytes_per_chunk,
+                                  chunks_per_layer) */
+    int32_t device;
+} aqz_reader_desc;
+/* Everything the reader will ever use is allocated here: the per-frame
+ * tables, the chunk table, a decoded-layer buffer (chunks at bytes_per_chunk
+ * rounded up to 16; only with codecs != 0), the staging buffer and the
+ * decoder's scratch (aqz_decompressor_scratch_bytes_for).  Loading and
+ * reading allocate no device memory. */
+aqz_status aqz_reader_create(const aqz_reader_desc* desc, aqz_reader** out);
+void aqz_reader_destroy(aqz_reader* r);
+/* Device bytes aqz_reader_create allocates for desc, exactly.  0 for an
+ * invalid description.  No GPU needed. */
+uint64_t aqz_reader_device_bytes(const aqz_reader_desc* desc);
+/* frame_bytes, frames_per_layer, chunks_per_layer, bytes_per_chunk; width and
+ * height are those of the frames handed back (acquisition orientation);
+ * chunk_pitch is the pitch of the reader's decoded-layer buffer; layer_slots 1. */
+aqz_status aqz_reader_layout(const aqz_reader* r, aqz_level_layout* out);
+
+/* Load a layer from n_frames frames lying back to back: frame i is bytes
+ * [offsets[i], offsets[i + 1]) of `frames` and holds chunk chunk_of_frame[i]
+ * of the layer (offsets: n_frames + 1 values, chunk_of_frame: n_frames; both
+ * host arrays, read before the call returns).  chunk_of_frame == NULL: the
+ * order aqz_stage_compress_layer writes (shard-major, aqz_stage_compressed_
+ * entries), with n_frames == chunks_per_layer.  Chunks not listed, and
+ * zero-length frames, are chunks never written.  mem: where `frames` lies --
+ * AQZ_MEM_HOST and AQZ_MEM_HOST_PINNED are copied into the reader's staging
+ * buffer (frames_bytes <= max_frames_bytes), AQZ_MEM_DEVICE is decoded in
+ * place and must stay valid until the load has run on `stream`.
+ * codec: the AQZ_CODEC_* the frames were written with.  AQZ_CODEC_NONE: a
+ * frame is the chunk itself (bytes_per_chunk long, else its status is
+ * AQZ_DECODE_BAD_HEADER); device frames are then borrowed until the next load.
+ * Enqueued on `stream` (hipStream_t; NULL = default) behind the reads of the
+ * previous layer enqueued so far, on whichever streams.
+ * AQZ_STATUS_INVALID_ARGUMENT (with an aqz_last_error text): a chunk_of_frame
+ * entry >= chunks_per_layer or listed twice, offsets that decrease or exceed
+ * frames_bytes, a codec the reader was not created for.  A malformed frame is
+ * a per-chunk status (aqz_reader_status), as in aqz_decompressor_run: the
+ * other chunks' pixels are exact, and the pixels of the bad chunk are
+ * unspecified but written only inside the destination frames. */
+aqz_status aqz_reader_load_frames(aqz_reader* r, const void* frames, size_t frames_bytes,
+                                  int32_t mem, const uint64_t* offsets,
+                                  const uint32_t* chunk_of_frame, uint32_t n_frames,
+                                  int32_t codec, void* stream);
+/* Load a layer of decoded chunks already on the device (e.g. what
+ * aqz_stage_device_layer returns): chunk c at chunks + c * pitch, pitch >=
+ * bytes_per_chunk.  has_data (device) NULL = every chunk present, else chunk
+ * c is present iff has_data[c] == tag.  Nothing is copied: the chunks are
+ * borrowed until the next load. */
+aqz_status aqz_reader_load_chunks(aqz_reader* r, const void* chunks, uint64_t pitch,
+                                  const uint32_t* has_data, uint32_t tag, void* stream);
+/* Frames [first, first + count) of the loaded layer (ids inside the layer, in
+ * acquisition order) -> dst + i * dst_stride (device), row-major.  Only bytes
+ * [0, frame_bytes) of each destination frame are written; dst_stride >=
+ * frame_bytes, any alignment.  Enqueued on `stream` behind the load; returns
+ * at once.  A range outside the layer or a dst_stride below frame_bytes is
+ * AQZ_STATUS_INVALID_ARGUMENT. */
+aqz_status aqz_reader_read_frames(aqz_reader* r, uint32_t first, uint32_t count, void* dst,
+                                  uint64_t dst_stride, void* stream);
+/* Waits for the last load.  status (chunks_per_layer values, may be NULL):
+ * the AQZ_DECODE_* of every chunk by chunk index, AQZ_DECODE_SKIPPED for
+ * chunks never written; *n_bad = chunks with an error status. */
+aqz_status aqz_reader_status(aqz_reader* r, uint32_t* status, size_t cap, uint32_t* n_bad);
+
 #ifdef __cplusplus
 }
 #endif
