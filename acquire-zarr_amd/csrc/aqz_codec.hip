@@ -88,7 +88,7 @@ stream_ref(const BloscGeom& g, uint32_t q)
 
 // Byte x (0 <= x < bsize) of the shuffled block (c-blosc 1.x shuffle /
 // bitshuffle; a block whose element count is not a multiple of 8 is not
-// bit-shuffled).
+// bit-shuffled; the bytes after a block's last whole element stay in place).
 __device__ __forceinline__ uint8_t
 shuffled_byte(const uint8_t* blk, uint32_t bsize, uint32_t ts, uint32_t sh, uint32_t x)
 {
@@ -99,7 +99,9 @@ shuffled_byte(const uint8_t* blk, uint32_t bsize, uint32_t ts, uint32_t sh, uint
         const uint32_t jj = x / ne, i = x - jj * ne;
         return blk[i * ts + jj];
     }
-    if (sh == 2 && ne % 8 == 0 && ne * ts == bsize) {
+    if (sh == 2 && ne % 8 == 0 && ne > 0) {
+        if (x >= ne * ts)
+            return blk[x];
         const uint32_t row = ne / 8;
         const uint32_t r = x / row, m = x - r * row;
         const uint32_t jj = r >> 3, b = r & 7u;
@@ -692,7 +694,10 @@ shuffle_blocks(const ShuffleParams p)
             dst[x] = src[x];
         return;
     }
-    if (p.shuffle == 2 && ne % 8 == 0 && ne * ts == bsize) {
+    if (p.shuffle == 2 && ne % 8 == 0 && ne > 0) {
+        if (part == 0) // the bytes after the last whole element
+            for (uint32_t x = ne * ts + t; x < bsize; x += 256)
+                dst[x] = src[x];
         const uint32_t row = ne / 8;
         const uint32_t lo = uint32_t(uint64_t(row) * part / np);
         const uint32_t hi = uint32_t(uint64_t(row) * (part + 1) / np);

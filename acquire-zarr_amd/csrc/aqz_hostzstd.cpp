@@ -117,9 +117,10 @@ unshuffle_block(int sh, uint32_t ts, const uint8_t* src, uint8_t* dst, uint32_t 
             for (uint32_t i = 0; i < ne; ++i)
                 dst[i * ts + j] = src[j * ne + i];
         std::memcpy(dst + ne * ts, src + ne * ts, n - ne * ts);
-    } else if (sh == 2 && ne % 8 == 0 && ne * ts == n) {
+    } else if (sh == 2 && ne % 8 == 0 && ne > 0) {
         const uint32_t row = ne / 8;
-        std::memset(dst, 0, n);
+        std::memset(dst, 0, ne * ts);
+        std::memcpy(dst + ne * ts, src + ne * ts, n - ne * ts);
         for (uint32_t r = 0; r < 8 * ts; ++r) {
             const uint32_t j = r >> 3, b = r & 7u;
             for (uint32_t m = 0; m < row; ++m) {

@@ -223,7 +223,8 @@ lz4_decode(Io& io, uint32_t n_src, uint32_t n_dst)
 
 // Does a block of bsize bytes go through the element-wise un-shuffle?  (A
 // bit-shuffled block whose element count is no multiple of 8 was stored as
-// it is.)
+// it is; the bytes after the last whole element of any block were, as
+// c-blosc's shuffles leave them.)
 AQZ_HD inline bool
 block_is_shuffled(uint32_t bsize, uint32_t ts, uint32_t mode)
 {
@@ -231,7 +232,7 @@ block_is_shuffled(uint32_t bsize, uint32_t ts, uint32_t mode)
     if (mode == 1)
         return ne > 0;
     if (mode == 2)
-        return ne % 8 == 0 && ne * ts == bsize && ne > 0;
+        return ne % 8 == 0 && ne > 0;
     return false;
 }
 

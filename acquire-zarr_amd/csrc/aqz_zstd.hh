@@ -7,14 +7,23 @@
 //   frame    magic, Single_Segment descriptor + Frame_Content_Size, no
 //            checksum, no dictionary (ZSTD_compress's defaults)
 //   blocks   Raw, RLE or Compressed; at most kBlock bytes of content
-//   literals Raw, RLE, or Huffman in 4 streams; the first Huffman block of
-//            a frame carries the tree description (weights FSE-compressed,
-//            or direct when <= 128 weights), later blocks reuse it
-//            (Treeless literals)
-//   sequences none, or LZ matches coded with the predefined FSE
-//            distributions of literal length, match length and offset codes
-//            (Symbol_Compression_Modes = 0); offsets are always new offsets
-//            (Offset_Value = offset + 3, no repeat codes)
+//   literals Raw, or Huffman in 4 streams (never RLE literals: a block of
+//            one byte value is an RLE block); the first Huffman block of a
+//            group of blocks (aqz_codec.hh kHufGroup / kHufGroupPlainLog2)
+//            carries the group's tree description (weights FSE-compressed,
+//            or direct when <= 128 weights and that is no longer), the
+//            group's other Huffman blocks reuse it (Treeless literals)
+//   sequences none, or LZ matches coded per segment (one frame) with either
+//            the predefined FSE distributions of literal length, offset and
+//            match length codes (Symbol_Compression_Modes = 0 in every
+//            block), or distributions fitted to the segment's code counts
+//            (accuracy log 5..9, fse_write_ncount) when the three cost less
+//            with their descriptions: the segment's first block with
+//            sequences carries the three descriptions (FSE_Compressed_Mode
+//            for all three), its later blocks repeat them (Repeat_Mode for
+//            all three); the modes are never mixed and never RLE_Mode.
+//            Offsets are always new offsets (Offset_Value = offset + 3 <
+//            2^24, no repeat codes)
 //
 // The FSE table construction and state transitions follow the normative
 // decoding tables of RFC 8878 4.1.1 (spread step (size>>1)+(size>>3)+3,

@@ -60,12 +60,15 @@ or_unshuffle(size_t ts, size_t n, const uint8_t* src, uint8_t* dst)
 /* ---- bitshuffle of one block (c-blosc 1.x): when the block holds a
  * multiple of 8 elements it is transposed to ts*8 bit-planes (plane
  * r = 8*byte + bit, each ne/8 bytes; bit k of plane byte m = that bit of
- * element 8m+k); any other block is copied unchanged. */
+ * element 8m+k) and the bytes after its last whole element are copied, as
+ * c-blosc's decoder inverts it (c-blosc's own blocks are whole elements; a
+ * frame with another block size meets the rule in its last block); a block of
+ * any other element count is copied unchanged. */
 void
 or_bitshuffle(size_t ts, size_t n, const uint8_t* src, uint8_t* dst)
 {
     const size_t ne = n / ts;
-    if (ne % 8 != 0 || ne * ts != n) {
+    if (ne % 8 != 0) {
         memcpy(dst, src, n);
         return;
     }
@@ -83,7 +86,7 @@ void
 or_bitunshuffle(size_t ts, size_t n, const uint8_t* src, uint8_t* dst)
 {
     const size_t ne = n / ts;
-    if (ne % 8 != 0 || ne * ts != n) {
+    if (ne % 8 != 0) {
         memcpy(dst, src, n);
         return;
     }

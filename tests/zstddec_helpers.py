@@ -52,6 +52,43 @@ def zstd_compress2(data: bytes, level: int, window_log: int = 0, checksum: bool 
         L.ZSTD_freeCCtx(ctx)
 
 
+class _ZBuf(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
+
+
+def block_regen_sizes(frame: bytes, info: dict, nbytes: int):
+    """The bytes each block of a valid frame regenerates, by libzstd's streaming
+    decoder fed one block at a time (it decodes a block when its last byte is
+    in); and the decoded bytes."""
+    L = libzstd()
+    L.ZSTD_createDStream.restype = C.c_void_p
+    L.ZSTD_freeDStream.argtypes = [C.c_void_p]
+    L.ZSTD_initDStream.argtypes = [C.c_void_p]
+    L.ZSTD_initDStream.restype = C.c_size_t
+    L.ZSTD_decompressStream.argtypes = [C.c_void_p, C.POINTER(_ZBuf), C.POINTER(_ZBuf)]
+    L.ZSTD_decompressStream.restype = C.c_size_t
+    zds = C.c_void_p(L.ZSTD_createDStream())
+    try:
+        assert not L.ZSTD_isError(L.ZSTD_initDStream(zds))
+        src = C.create_string_buffer(bytes(frame), len(frame))
+        dst = C.create_string_buffer(max(1, nbytes))
+        out = _ZBuf(C.addressof(dst), nbytes, 0)
+        inp = _ZBuf(C.addressof(src), 0, 0)
+        sizes = []
+        ends = [b["pos"] + 3 + (1 if b["type"] == "rle" else b["size"]) for b in info["blocks"]]
+        for end in ends:
+            inp.size = end
+            before = out.pos
+            r = L.ZSTD_decompressStream(zds, C.byref(out), C.byref(inp))
+            assert not L.ZSTD_isError(r), r
+            assert inp.pos == end
+            sizes.append(out.pos - before)
+        assert r == 0, "the frame is not finished at its last block"
+        return sizes, dst.raw[:out.pos]
+    finally:
+        L.ZSTD_freeDStream(zds)
+
+
 # ---- inspector -------------------------------------------------------------------
 def _lit_header(b: bytes, p: int):
     """(type, streams, regenerated, compressed or None, header bytes) at b[p]."""
@@ -69,6 +106,64 @@ def _lit_header(b: bytes, p: int):
     return t, 1 if sf == 0 else 4, v & ((1 << bits) - 1), (v >> bits) & ((1 << bits) - 1), hdr
 
 
+MAX_LOG = (9, 8, 9)        # literal lengths, offsets, match lengths
+MAX_SYMBOLS = (36, 32, 53)
+
+
+def read_ncount(buf: bytes, pos: int, max_log: int):
+    """An FSE table description at buf[pos] (RFC 8878 4.1.1): (normalised counts
+    with -1 for "less than 1", accuracy log, bytes used)."""
+    acc = int.from_bytes(buf[pos:pos + 512], "little")
+    have = 8 * len(buf[pos:pos + 512])
+    at = 0
+
+    def read(n):
+        nonlocal at
+        v = (acc >> at) & ((1 << n) - 1)
+        at += n
+        return v
+
+    log = 5 + read(4)
+    assert log <= max_log, (log, max_log)
+    remaining = 1 << log
+    norm = []
+    while remaining > 0:
+        width = (remaining + 1).bit_length()
+        low_mask = (1 << (width - 1)) - 1
+        small = (1 << width) - 1 - (remaining + 1)   # values below it take width - 1 bits
+        v = (acc >> at) & ((1 << width) - 1)
+        if (v & low_mask) < small:
+            v &= low_mask
+            at += width - 1
+        else:
+            at += width
+            if v > low_mask:
+                v -= small
+        p = v - 1
+        remaining -= abs(p)
+        assert remaining >= 0, "probabilities exceed the table"
+        norm.append(p)
+        if p == 0:
+            while True:
+                r = read(2)
+                norm += [0] * r
+                if r != 3:
+                    break
+        assert len(norm) <= 256
+    assert at <= have, "description runs past the buffer"
+    return norm, log, (at + 7) // 8
+
+
+def _zero_repeat(norm):
+    """The longest count of zero probabilities a description's repeat flags
+    carry: a run of zeros less its first (which is coded as a value)."""
+    best = run = 0
+    for c in norm:
+        run = run + 1 if c == 0 else 0
+        best = max(best, run)
+    return max(0, best - 1)
+
+
 def frame_header(frame: bytes):
     """The frame-header features alone (info["blocks"] empty)."""
     return inspect(frame, blocks=False)
@@ -77,7 +172,11 @@ def frame_header(frame: bytes):
 def inspect(frame: bytes, blocks: bool = True):
     """Frame-header features and, per block, type / size and (compressed blocks)
     the literals type, stream count, weight coding, sequence count and table
-    modes, with the positions the mutations patch."""
+    modes, with the positions the mutations patch; of a block that describes
+    sequence tables, each table as read_ncount reads it ("tables"), and where all
+    three are FSE_Compressed their accuracy logs ("table_logs"), whether a
+    probability is -1 ("minus1") and the longest zero run the repeat flags carry
+    ("zero_repeat")."""
     f = bytes(frame)
     assert struct.unpack_from("<I", f, 0)[0] == MAGIC
     d = f[4]
@@ -127,7 +226,26 @@ def inspect(frame: bytes, blocks: bool = True):
             if n:
                 m = f[sp + cb]
                 blk["modes"] = (MODES[m >> 6], MODES[(m >> 4) & 3], MODES[(m >> 2) & 3])
-                blk["tables_pos"] = sp + cb + 1
+                blk["tables_pos"] = tp = sp + cb + 1
+                # the descriptions, in the order LL, OF, ML: FSE_Compressed tables
+                # are read, an RLE table is its one symbol
+                blk["tables"] = []
+                for k, mode in enumerate(blk["modes"]):
+                    tab = None
+                    if mode == "fse":
+                        norm, log, used = read_ncount(f[:body + size], tp, MAX_LOG[k])
+                        assert len(norm) <= MAX_SYMBOLS[k], (k, len(norm))
+                        tab = dict(norm=norm, log=log, nbytes=used, minus1=-1 in norm,
+                                   zero_repeat=_zero_repeat(norm))
+                        tp += used
+                    elif mode == "rle":
+                        tp += 1
+                    blk["tables"].append(tab)
+                blk["tables_end"] = tp
+                if blk["modes"] == ("fse", "fse", "fse"):
+                    blk["table_logs"] = tuple(t["log"] for t in blk["tables"])
+                    blk["minus1"] = any(t["minus1"] for t in blk["tables"])
+                    blk["zero_repeat"] = max(t["zero_repeat"] for t in blk["tables"])
         info["blocks"].append(blk)
         pos = body + (1 if btype == 1 else size)
         if last:
