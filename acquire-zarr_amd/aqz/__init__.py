@@ -141,6 +141,12 @@ class LevelLayoutC(C.Structure):
                 ("chunk_pitch", C.c_uint64)]
 
 
+class DecodeCountsC(C.Structure):
+    """aqz_decode_counts (include/aqz_gpu_bench.h)."""
+    _fields_ = [("zstd_parallel_frames", C.c_uint32), ("zstd_serial_frames", C.c_uint32),
+                ("zstd_blocks", C.c_uint32), ("zstd_sequences", C.c_uint32)]
+
+
 class ReaderDescC(C.Structure):
     _fields_ = [("dimensions", C.POINTER(Dimension)),
                 ("dimension_count", C.c_size_t),
@@ -285,6 +291,7 @@ def lib():
         "aqz_decompressor_destroy": ([vp], None),
         "aqz_decompressor_scratch_bytes": ([u64, u32], u64),
         "aqz_decompressor_scratch_bytes_for": ([u64, u32, u32], u64),
+        "aqz_decompressor_last_run_counts": ([vp, C.POINTER(DecodeCountsC)], i32),
         "aqz_stage_verify_prepare": ([vp, u32], i32),
         "aqz_decompressor_run": ([vp, vp, sz, vp, u32, vp, u64, u64, vp, vp], i32),
         "aqz_stage_verify_layer": ([vp, u32, u64, vp, sz], i32),
@@ -988,6 +995,10 @@ AQZ_DECODE_OK, AQZ_DECODE_SKIPPED, AQZ_DECODE_BAD_HEADER = DECODE_OK, DECODE_SKI
 AQZ_DECODE_CORRUPT, AQZ_DECODE_UNSUPPORTED = DECODE_CORRUPT, DECODE_UNSUPPORTED
 DECODE_CODEC_LZ4, DECODE_CODEC_ZSTD = 1, 2
 AQZ_DECODE_CODEC_LZ4, AQZ_DECODE_CODEC_ZSTD = DECODE_CODEC_LZ4, DECODE_CODEC_ZSTD
+# option bit of a codecs mask, with DECODE_CODEC_ZSTD only: plain zstd frames
+# through the block-parallel kernels
+DECODE_ZSTD_PARALLEL = 4
+AQZ_DECODE_ZSTD_PARALLEL = DECODE_ZSTD_PARALLEL
 UINT32_MAX = (1 << 32) - 1
 
 
@@ -1035,6 +1046,16 @@ class Decompressor:
         _check(lib().aqz_decompressor_run(self.h, frames_ptr, frames_bytes, offsets_ptr,
                                           n_chunks, dst_ptr, pitch, chunk_bytes, status_ptr,
                                           stream_ptr), "aqz_decompressor_run")
+
+    def last_run_counts(self):
+        """What the last run did with its zstd frames (aqz_decompressor_last_run_counts;
+        waits for it): {"parallel_frames", "serial_frames", "blocks", "sequences"}.
+        All zero unless the decoder was created with DECODE_ZSTD_PARALLEL."""
+        c = DecodeCountsC()
+        _check(lib().aqz_decompressor_last_run_counts(self.h, C.byref(c)),
+               "aqz_decompressor_last_run_counts")
+        return dict(parallel_frames=c.zstd_parallel_frames, serial_frames=c.zstd_serial_frames,
+                    blocks=c.zstd_blocks, sequences=c.zstd_sequences)
 
 
 def shard_table(offsets, extents) -> bytes:

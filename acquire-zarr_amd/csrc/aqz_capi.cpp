@@ -1181,7 +1181,8 @@ aqz_decompressor_create(uint64_t max_chunk_bytes, uint32_t max_chunks, aqz_decom
     });
 }
 
-static_assert(AQZ_DECODE_CODEC_LZ4 == dec::kFamilyLz4 && AQZ_DECODE_CODEC_ZSTD == dec::kFamilyZstd,
+static_assert(AQZ_DECODE_CODEC_LZ4 == dec::kFamilyLz4 && AQZ_DECODE_CODEC_ZSTD == dec::kFamilyZstd &&
+                AQZ_DECODE_ZSTD_PARALLEL == kDecodeZstdParallel,
               "decode codec bits");
 
 aqz_status
@@ -1191,7 +1192,7 @@ aqz_decompressor_create_for(uint64_t max_chunk_bytes, uint32_t max_chunks, uint3
     if (!out)
         return AQZ_STATUS_INVALID_ARGUMENT;
     *out = nullptr;
-    if (codecs == 0 || (codecs & ~(AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD)))
+    if (!decode_codecs_valid(codecs))
         return AQZ_STATUS_INVALID_ARGUMENT;
     return guard([&] {
         auto h = std::make_unique<aqz_decompressor>();
@@ -1219,6 +1220,21 @@ aqz_decompressor_scratch_bytes_for(uint64_t max_chunk_bytes, uint32_t max_chunks
 }
 
 aqz_status
+aqz_decompressor_last_run_counts(aqz_decompressor* d, aqz_decode_counts* out)
+{
+    if (!d || !out)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    return guard_sticky(d, [&] {
+        uint32_t c[4];
+        d->d->last_run_counts(c);
+        out->zstd_parallel_frames = c[0];
+        out->zstd_serial_frames = c[1];
+        out->zstd_blocks = c[2];
+        out->zstd_sequences = c[3];
+    });
+}
+
+aqz_status
 aqz_decompressor_run(aqz_decompressor* d, const void* frames, size_t frames_bytes,
                      const uint64_t* offsets, uint32_t n_chunks, void* dst, uint64_t pitch,
                      uint64_t chunk_bytes, uint32_t* status, void* stream)
@@ -1243,7 +1259,7 @@ aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer, const void
 aqz_status
 aqz_stage_verify_prepare(aqz_stage* st, uint32_t codecs)
 {
-    if (codecs == 0 || (codecs & ~(AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD)))
+    if (!decode_codecs_valid(codecs))
         return AQZ_STATUS_INVALID_ARGUMENT;
     return guard_sticky(st, [&] { st->st->verify_prepare(codecs); });
 }

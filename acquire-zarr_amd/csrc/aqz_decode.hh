@@ -53,6 +53,16 @@ struct DecodeParams
     uint8_t* zlit;
     uint64_t zlit_pitch;
     uint32_t zpasses;
+    // launch_zstd_parallel only (aqz_zstdpar.hip); zfr == nullptr: not in use.
+    // zfr[2q]: 0 = frame q is zstd_decode's, else 1 + the blocks indexed (the
+    // frame is the parallel kernels'); zfr[2q + 1]: its sequences.  zcounts:
+    // the four words of aqz_decode_counts.  zpar: per chunk (zpar_pitch) the
+    // block table, the literal area and the records (zstd_parallel_layout).
+    uint32_t* zfr;
+    uint32_t* zcounts;
+    uint8_t* zpar;
+    uint64_t zpar_pitch, zpar_lit_off, zpar_rec_off;
+    uint32_t zpar_cap;
 };
 
 // Enqueue: status (and bad) cleared, frames decoded, large blocks un-shuffled.
@@ -67,5 +77,22 @@ uint64_t zstd_decode_lit_pitch(uint64_t max_chunk_bytes);
 // run's zstd frames -- plain zstd, blosc1 with the zstd codec (memcpyed ones
 // included) -- decoded; other frames are not touched.
 hipError_t launch_zstd_decode(const DecodeParams& p, hipStream_t stream);
+
+// The block-parallel path of plain zstd frames (AQZ_DECODE_ZSTD_PARALLEL).
+// Per chunk of up to max_chunk_bytes: a table of cap blocks, then the literal
+// area, then the records; pitch bytes in all.
+struct ZstdParLayout
+{
+    uint64_t lit_off, rec_off, pitch;
+    uint32_t cap;
+};
+ZstdParLayout zstd_parallel_layout(uint64_t max_chunk_bytes);
+// Device bytes the path adds: the chunks' slots, two words per chunk and the
+// four count words.
+uint64_t zstd_parallel_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks);
+// Enqueue between launch_blosc_decode and launch_zstd_decode: the plain zstd
+// frames whose blocks fit the table are decoded (or get their status) and
+// marked in zfr; zstd_decode then skips them, zstd_finish does not.
+hipError_t launch_zstd_parallel(const DecodeParams& p, hipStream_t stream);
 
 } // namespace aqz

@@ -2665,8 +2665,9 @@ Decompressor::Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool b
 {
     if (max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull || max_chunks == 0)
         throw Error(1, "chunk size outside the blosc1 limits, or no chunks");
-    if (codecs == 0 || (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd)))
-        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD");
+    if (!decode_codecs_valid(codecs))
+        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD, "
+                       "AQZ_DECODE_ZSTD_PARALLEL only with the latter alone");
     const bool zstd = codecs & dec::kFamilyZstd;
     if (big_blocks || zstd) {
         scratch_pitch_ = (max_chunk_bytes + 15) & ~uint64_t(15);
@@ -2677,14 +2678,28 @@ Decompressor::Decompressor(uint64_t max_chunk_bytes, uint32_t max_chunks, bool b
         zlit_pitch_ = zstd_decode_lit_pitch(max_chunk_bytes);
         zlit_.alloc(zlit_pitch_ * zpasses_ * max_chunks);
     }
+    if (codecs & kDecodeZstdParallel) {
+        zpar_.alloc(zstd_parallel_bytes(max_chunk_bytes, max_chunks));
+        // counts of "the last run" before any run: zeros
+        hip_check(hipMemset(zpar_.p, 0, 16), "hipMemset");
+    }
+}
+
+bool
+decode_codecs_valid(uint32_t codecs)
+{
+    const uint32_t fam = codecs & (dec::kFamilyLz4 | dec::kFamilyZstd);
+    if (fam == 0 || (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd | kDecodeZstdParallel)))
+        return false;
+    // the option bit: a decoder for the zstd family alone
+    return !(codecs & kDecodeZstdParallel) || codecs == (dec::kFamilyZstd | kDecodeZstdParallel);
 }
 
 uint64_t
 Decompressor::scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks, bool big_blocks,
                             uint32_t codecs)
 {
-    if (max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull || codecs == 0 ||
-        (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd)))
+    if (max_chunk_bytes == 0 || max_chunk_bytes > 0x7fffffefull || !decode_codecs_valid(codecs))
         return 0;
     const bool zstd = codecs & dec::kFamilyZstd;
     uint64_t n = 0;
@@ -2693,6 +2708,8 @@ Decompressor::scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks, bool 
     if (zstd)
         n += zstd_decode_lit_pitch(max_chunk_bytes) * zstd_decode_passes(max_chunk_bytes) *
              max_chunks;
+    if (codecs & kDecodeZstdParallel)
+        n += zstd_parallel_bytes(max_chunk_bytes, max_chunks);
     return n;
 }
 
@@ -2720,14 +2737,37 @@ Decompressor::run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* 
     p.bad = bad;
     p.scratch = scratch_.p;
     p.scratch_pitch = scratch_pitch_;
-    p.codecs = codecs_;
+    p.codecs = codecs_ & (dec::kFamilyLz4 | dec::kFamilyZstd);
     p.zlit = zlit_.p;
     p.zlit_pitch = zlit_pitch_;
     p.zpasses = zpasses_;
+    if (zpar_.p) {
+        const ZstdParLayout l = zstd_parallel_layout(max_chunk_bytes_);
+        p.zcounts = reinterpret_cast<uint32_t*>(zpar_.p);
+        p.zfr = reinterpret_cast<uint32_t*>(zpar_.p + 16);
+        p.zpar = zpar_.p + 16 + ((uint64_t(max_chunks_) * 8 + 15) & ~uint64_t(15));
+        p.zpar_pitch = l.pitch;
+        p.zpar_lit_off = l.lit_off;
+        p.zpar_rec_off = l.rec_off;
+        p.zpar_cap = l.cap;
+    }
     // clears the status words and takes the LZ4, memcpyed and zero-length frames
     hip_check(launch_blosc_decode(p, stream), "blosc decode launch");
+    if (zpar_.p) // plain zstd frames, ahead of the serial kernel that takes the rest
+        hip_check(launch_zstd_parallel(p, stream), "zstd parallel decode launch");
     if (codecs_ & dec::kFamilyZstd)
         hip_check(launch_zstd_decode(p, stream), "zstd decode launch");
+    last_stream_ = stream;
+}
+
+void
+Decompressor::last_run_counts(uint32_t (&counts)[4])
+{
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (!zpar_.p)
+        return;
+    hip_check(hipStreamSynchronize(last_stream_), "hipStreamSynchronize");
+    hip_check(hipMemcpy(counts, zpar_.p, 16, hipMemcpyDeviceToHost), "hipMemcpy");
 }
 
 // per slot: the word buffers (allocated by the first use), the event and the
@@ -2750,16 +2790,20 @@ ensure_verify_slots(StageLevel& L)
 void
 Stage::verify_prepare(uint32_t codecs)
 {
-    if (codecs == 0 || (codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd)))
-        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD");
+    if (!decode_codecs_valid(codecs))
+        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD, "
+                       "AQZ_DECODE_ZSTD_PARALLEL only with the latter alone");
+    const uint32_t zcodecs = dec::kFamilyZstd | (codecs & kDecodeZstdParallel);
     for (StageLevel& L : lv_) {
         if (!L.ring.p)
             continue;
         ensure_verify_slots(L);
         if ((codecs & dec::kFamilyLz4) && !L.dec)
             L.dec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false);
-        if ((codecs & dec::kFamilyZstd) && !L.zdec) {
-            L.zdec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false, dec::kFamilyZstd);
+        if ((codecs & dec::kFamilyZstd) && (!L.zdec || L.zdec->codecs() != zcodecs)) {
+            if (L.zdec) // prepared before without (or with) the option bit
+                hip_check(hipStreamSynchronize(comp_stream(L)), "hipStreamSynchronize");
+            L.zdec = std::make_unique<Decompressor>(L.bpc, L.n_chunks, false, zcodecs);
             L.voffsets.alloc((size_t(L.n_chunks) + 1) * 8);
         }
         const size_t words = size_t(L.n_chunks) * 2 * 4;

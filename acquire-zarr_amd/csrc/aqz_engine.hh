@@ -217,6 +217,13 @@ class Compressor
 // when created for them, of blosc1-zstd and plain zstd frames
 // (aqz_zstddec.hip): the frames of n_chunks chunks back to back in device
 // memory -> chunk i at dst + i * pitch and a status word per frame.
+// Option bit of a decoder's codecs mask (== AQZ_DECODE_ZSTD_PARALLEL): plain
+// zstd frames go through the block-parallel kernels (aqz_zstdpar.hip).
+constexpr uint32_t kDecodeZstdParallel = 4;
+// a family at least, no unknown bit, the option bit only in the mask
+// kFamilyZstd | kDecodeZstdParallel
+bool decode_codecs_valid(uint32_t codecs);
+
 class Decompressor
 {
   public:
@@ -239,8 +246,11 @@ class Decompressor
              uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
              uint32_t* status, hipStream_t stream, const uint32_t* order = nullptr,
              uint32_t* bad = nullptr);
-    uint64_t device_bytes() const { return scratch_.n + zlit_.n; }
+    uint64_t device_bytes() const { return scratch_.n + zlit_.n + zpar_.n; }
     uint32_t codecs() const { return codecs_; }
+    // Waits for the last run; the four words of aqz_decode_counts (zeros from a
+    // decoder without kDecodeZstdParallel, which keeps none).
+    void last_run_counts(uint32_t (&counts)[4]);
 
   private:
     uint64_t max_chunk_bytes_;
@@ -250,6 +260,8 @@ class Decompressor
     uint64_t zlit_pitch_ = 0;
     uint32_t zpasses_ = 0;
     DevBuf scratch_, zlit_;
+    DevBuf zpar_; // count words, frame words, the chunks' slots (zstd_parallel_bytes)
+    hipStream_t last_stream_ = nullptr;
 };
 
 struct ArrayDesc

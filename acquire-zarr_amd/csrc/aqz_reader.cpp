@@ -41,8 +41,9 @@ struct Reader::Sizes
 Reader::Sizes
 Reader::sizes(const ReaderDesc& d, const ArrayDimensions& ad)
 {
-    if (d.codecs & ~(dec::kFamilyLz4 | dec::kFamilyZstd))
-        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD, or 0");
+    if (d.codecs && !decode_codecs_valid(d.codecs))
+        throw Error(1, "codecs: AQZ_DECODE_CODEC_LZ4 | AQZ_DECODE_CODEC_ZSTD, or 0; "
+                       "AQZ_DECODE_ZSTD_PARALLEL only with the latter alone");
     Sizes s;
     const uint64_t F = ad.frames_per_chunk_layer();
     if (F == 0 || F > 0x7fffffffull)

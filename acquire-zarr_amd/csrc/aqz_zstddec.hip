@@ -162,6 +162,8 @@ zstd_decode(DecodeParams p)
     // codecs are blosc_decode's
     if (!frame_ref(p, q, r) || r.len == 0 || dec::frame_family(r.f, r.len) != dec::kFamilyZstd)
         return;
+    if (p.zfr && p.zfr[2 * q] != 0) // decoded (or refused) by the parallel path
+        return;
     const uint32_t len = uint32_t(r.len);
     uint8_t* scr = p.scratch + uint64_t(q) * p.scratch_pitch;
     uint8_t* lit = p.zlit + (uint64_t(q) * p.zpasses + blockIdx.y) * p.zlit_pitch;

@@ -654,13 +654,24 @@ aqz_status aqz_stage_finalize(aqz_stage* st);
                                     the expected length, a header that does not fit.) */
 #define AQZ_DECODE_CODEC_LZ4 1u  /* blosc1 frames with the LZ4 codec, memcpyed frames */
 #define AQZ_DECODE_CODEC_ZSTD 2u /* blosc1 frames with the zstd codec, plain zstd frames */
+/* Option bit of a codecs mask, valid only as AQZ_DECODE_CODEC_ZSTD | AQZ_DECODE_ZSTD_PARALLEL
+ * (alone, or in a mask that also lists AQZ_DECODE_CODEC_LZ4, it is
+ * AQZ_STATUS_INVALID_ARGUMENT and 0 bytes: a decoder with the option serves the zstd family
+ * only, and LZ4 frames of its runs are AQZ_DECODE_UNSUPPORTED): plain zstd frames are decoded by block-parallel
+ * kernels (entropy decode of all blocks at once, literal copies out of the match chain)
+ * instead of one wave walking the frame.  The same frames are accepted, with the same
+ * statuses and the same bytes; blosc1-zstd frames, and a plain frame with more than
+ * max_chunk_bytes / 1024 + 16 blocks, are decoded by the serial kernel in the same run.
+ * It costs the scratch aqz_decompressor_scratch_bytes_for describes. */
+#define AQZ_DECODE_ZSTD_PARALLEL 4u
 typedef struct aqz_decompressor aqz_decompressor;
 /* A decoder with device scratch for runs of up to max_chunks frames of up to
  * max_chunk_bytes each (aqz_decompressor_scratch_bytes).  It decodes
  * AQZ_DECODE_CODEC_LZ4 only. */
 aqz_status aqz_decompressor_create(uint64_t max_chunk_bytes, uint32_t max_chunks,
                                    aqz_decompressor** out);
-/* The same for the codecs listed (AQZ_DECODE_CODEC_* or-ed; 0 or unknown bits:
+/* The same for the codecs listed (AQZ_DECODE_CODEC_* or-ed, or
+ * AQZ_DECODE_CODEC_ZSTD | AQZ_DECODE_ZSTD_PARALLEL; no codec or unknown bits:
  * AQZ_STATUS_INVALID_ARGUMENT).  Zero-length frames are skipped chunks whatever
  * the codecs. */
 aqz_status aqz_decompressor_create_for(uint64_t max_chunk_bytes, uint32_t max_chunks,
@@ -676,7 +687,14 @@ uint64_t aqz_decompressor_scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_c
  * since zstd matches reach back farther than any on-chip window) plus the
  * Huffman-literal slots: min(max_chunk_bytes, 128 KiB) rounded up to 16, times
  * min(8, ceil(max_chunk_bytes / 32 KiB)) concurrent block decodes per chunk.
- * Nothing is allocated by aqz_decompressor_run.  0 on invalid arguments.  No
+ * AQZ_DECODE_ZSTD_PARALLEL adds, with n = max_chunk_bytes and r16 = "rounded
+ * up to 16":
+ *   max_chunks * (64 * (n / 1024 + 16)     the block table, 64 bytes a block
+ *                 + r16(n)                 Huffman literals of all blocks
+ *                 + r16(12 * (n / 3)))     12-byte sequence records; a sequence
+ *                                          regenerates at least 3 bytes
+ *   + r16(8 * max_chunks) + 16             two words per frame, the count words
+ * (divisions round down).  Nothing is allocated by aqz_decompressor_run.  0 on invalid arguments.  No
  * GPU needed. */
 uint64_t aqz_decompressor_scratch_bytes_for(uint64_t max_chunk_bytes, uint32_t max_chunks,
                                             uint32_t codecs);
@@ -711,8 +729,9 @@ aqz_status aqz_decompressor_run(aqz_decompressor* d, const void* frames, size_t 
 aqz_status aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer,
                                   const void* frames, size_t frames_bytes);
 /* Allocate now, for every level the stage splits on the device, the decoder state
- * aqz_stage_verify_layer needs for layers of the listed codecs (AQZ_DECODE_CODEC_* or-ed;
- * 0 or unknown bits: AQZ_STATUS_INVALID_ARGUMENT); aqz_stage_memory_usage reports it from
+ * aqz_stage_verify_layer needs for layers of the listed codecs (AQZ_DECODE_CODEC_* or-ed,
+ * or AQZ_DECODE_CODEC_ZSTD | AQZ_DECODE_ZSTD_PARALLEL, which the zstd decoder is then created with;
+ * no codec or unknown bits: AQZ_STATUS_INVALID_ARGUMENT); aqz_stage_memory_usage reports it from
  * this call on.  With AQZ_DECODE_CODEC_ZSTD that is, per level: the two words per chunk
  * and slot (device and pinned), and one zstd decoder for a layer slot's chunks
  * (aqz_decompressor_scratch_bytes_for(chunk bytes, chunks per layer,
@@ -722,7 +741,8 @@ aqz_status aqz_stage_verify_layer(aqz_stage* st, uint32_t level, uint64_t layer,
  * slots.  One decoder serves all slots of a level: verifies of a level run in order on
  * the hand-off stream.  Without this call nothing changes: zstd layers stay
  * AQZ_STATUS_NOT_YET_IMPLEMENTED and the first LZ4 verify allocates what it always did.
- * Calling it again adds the codecs not yet prepared. */
+ * Calling it again adds the codecs not yet prepared; a zstd decoder prepared with the
+ * other setting of AQZ_DECODE_ZSTD_PARALLEL is replaced. */
 aqz_status aqz_stage_verify_prepare(aqz_stage* st, uint32_t codecs);
 /* Waits.  *n_bad = chunks whose decoded bytes differ from the resident chunk or whose
  * decode status is an error.  A skipped chunk is good iff the resident chunk is all zero.
@@ -759,7 +779,9 @@ typedef struct
     size_t dimension_count;
     int32_t data_type;               /* AQZ_DTYPE_* */
     const size_t* storage_dimension_order; /* level 0 only; NULL = acquisition order */
-    uint32_t codecs;           /* AQZ_DECODE_CODEC_* or-ed; 0 = raw chunks only */
+    uint32_t codecs;           /* AQZ_DECODE_CODEC_* or-ed, or AQZ_DECODE_CODEC_ZSTD |
+                                  AQZ_DECODE_ZSTD_PARALLEL;
+                                  0 = raw chunks only */
     uint64_t max_frames_bytes; /* device staging for frames given in host memory;
                                   0 = aqz_compressor_max_bytes(bytes_per_chunk,
                                   chunks_per_layer) */

@@ -194,6 +194,22 @@ enum
 aqz_status aqz_probe_hbm(int32_t device, int32_t shape, uint64_t bytes, uint32_t reps,
                          double* ms, uint64_t* read_bytes);
 
+/* What the last aqz_decompressor_run of a decoder created with
+ * AQZ_DECODE_ZSTD_PARALLEL did with its zstd frames: device words the kernels
+ * bump, read back after waiting for that run.  A decoder created without the
+ * bit keeps no counts (all zero). */
+typedef struct
+{
+    uint32_t zstd_parallel_frames; /* plain zstd frames the parallel kernels took
+                                      (those they refused as malformed included) */
+    uint32_t zstd_serial_frames;   /* zstd frames left to the serial kernel:
+                                      blosc1-zstd frames, and plain frames with
+                                      more blocks than the block table holds */
+    uint32_t zstd_blocks;          /* compressed blocks entropy-decoded */
+    uint32_t zstd_sequences;       /* sequences the match chain walked */
+} aqz_decode_counts;
+aqz_status aqz_decompressor_last_run_counts(aqz_decompressor* d, aqz_decode_counts* out);
+
 #ifdef __cplusplus
 }
 #endif
