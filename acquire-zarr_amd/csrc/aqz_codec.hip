@@ -468,6 +468,44 @@ block_scan256(uint32_t v, uint32_t* total)
     return before + x - v;
 }
 
+// The same over 64-bit sums: the frames of a layer (scan_offsets) add up past
+// 2^32 bytes from five 1 GiB chunks on.
+__device__ uint64_t
+block_scan256_64(uint64_t v, uint64_t* total)
+{
+    __shared__ uint64_t wsum64[4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    unsigned long long x = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long y = __shfl_up(x, d);
+        if (int(lane) >= d)
+            x += y;
+    }
+    if (lane == 63)
+        wsum64[w] = x;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (uint32_t k = 0; k < 4; ++k) {
+        if (k < w)
+            before += wsum64[k];
+        all += wsum64[k];
+    }
+    __syncthreads();
+    *total = all;
+    return before + x - v;
+}
+
+// The per-chunk carry of chunk_layout and zstd_chunk stays below 2^32: a
+// chunk has nbytes <= 0x7fffffef bytes, and no record stores more than its
+// stream or segment holds (an LZ4 stream that does not shrink is stored raw,
+// lz4_streams; a zstd segment whose frame does not shrink is stored raw,
+// zstd_segment), so the records add up to nbytes at the most.  Each record
+// adds its 4-byte size word, each block its 4-byte start word.  A full block
+// is kLz4StreamMax * typesize bytes, split into typesize streams at the most
+// (make_blosc_geom), and one leftover block follows: at most
+// nbytes / 4096 + 2 blocks and nbytes / 4096 + 17 streams, so
+//   carry <= 16 + 4 * (2^19 + 2) + 4 * (2^19 + 17) + 0x7fffffef < 2^31 + 2^23.
+// blosc-zstd has 256 KiB segments, one record each: less still.
 __global__ __launch_bounds__(256) void
 chunk_layout(const BloscParams p)
 {
@@ -502,9 +540,9 @@ scan_offsets(const uint32_t* fsize, const uint32_t* order, uint64_t* offsets,
     for (uint32_t i0 = 0; i0 < n; i0 += 256) {
         const uint32_t i = i0 + threadIdx.x;
         const uint32_t c = i < n ? (order ? order[i] : i) : 0;
-        const uint32_t v = i < n ? fsize[c] : 0;
-        uint32_t tot;
-        const uint32_t pre = block_scan256(v, &tot);
+        const uint64_t v = i < n ? fsize[c] : 0;
+        uint64_t tot;
+        const uint64_t pre = block_scan256_64(v, &tot);
         const uint64_t carry = carry_s;
         if (i < n) {
             offsets[i] = carry + pre;

@@ -2334,6 +2334,11 @@ Compressor::run_zstd(const uint8_t* chunks, uint64_t pitch, uint32_t n_chunks,
     p.dbg = tune_.parse & 15u;
     const bool shuffle = blosc && !store_only_ &&
                          (c_.shuffle == 2 || (c_.shuffle == 1 && typesize_ > 1));
+    // the block shuffle's grid has the chunk as its y dimension
+    // (launch_shuffle_blocks): refused here, before anything is allocated
+    // or enqueued
+    if (shuffle && n_chunks > 65535u)
+        throw Error(1, "blosc-zstd with a shuffle takes at most 65535 chunks per run");
     if (shuffle) {
         alloc_large(zin_, size_t(n_chunks) * nbytes_, tune_.vmm);
         ShuffleParams sp{ chunks, pitch, n_chunks, flags, tag, p.nbytes, typesize_,

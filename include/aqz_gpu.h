@@ -529,7 +529,13 @@ uint32_t aqz_crc32c(const void* data, size_t n);
 /* Stand-alone compressor (any AQZ_CODEC_*) for device-resident chunk arrays: chunk i of
  * n_chunks at chunks + i * pitch, chunk_bytes each; frames back to back at
  * dst (device, >= aqz_compressor_max_bytes), offsets (device, n_chunks + 1
- * uint64) as above.  Enqueued on `stream` (hipStream_t; NULL = default). */
+ * uint64) as above.  Enqueued on `stream` (hipStream_t; NULL = default).
+ * The frames of a run may add up to any size (the offsets are summed in 64
+ * bits: five incompressible 1 GiB chunks pass 4 GiB).  One limit on the chunk
+ * count: AQZ_CODEC_BLOSC_ZSTD with a shuffle that moves bytes (bit shuffle, or
+ * byte shuffle of a typesize above 1) at clevel >= 1 takes at most 65535 chunks
+ * per run; more is AQZ_STATUS_INVALID_ARGUMENT before anything is enqueued
+ * (the same for a stage layer of that many chunks). */
 typedef struct aqz_compressor aqz_compressor;
 aqz_status aqz_compressor_create(uint64_t chunk_bytes, uint32_t typesize,
                                  const aqz_compression* comp, aqz_compressor** out);
