@@ -156,6 +156,25 @@ class ReaderDescC(C.Structure):
                 ("device", C.c_int32)]
 
 
+class RegionC(C.Structure):
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32)]
+
+
+def _region(region):
+    """(x0, y0, width, height) in pixels of the frames handed back -> aqz_region*
+    (None stays NULL)"""
+    return None if region is None else C.byref(RegionC(*region))
+
+
+def _region_chunks(fn, h, what, first, count, region):
+    n = C.c_uint32(0)
+    _check(fn(h, first, count, _region(region), None, 0, C.byref(n)), what)
+    out = np.empty(n.value, dtype=np.uint32)
+    _check(fn(h, first, count, _region(region), out.ctypes.data, n.value, C.byref(n)), what)
+    return out
+
+
 def build_library(force: bool = False) -> str:
     """Compile libaqz_gpu.so for gfx950 in-tree (hipcc, no GPU needed)."""
     if force or not os.path.exists(LIB_PATH):
@@ -316,6 +335,13 @@ def lib():
         "aqz_reader_load_chunks": ([vp, vp, u64, vp, u32, vp], i32),
         "aqz_reader_read_frames": ([vp, u32, u32, vp, u64, vp], i32),
         "aqz_reader_status": ([vp, vp, sz, C.POINTER(u32)], i32),
+        "aqz_dims_region_chunks": ([vp, u32, u32, C.POINTER(RegionC), vp, sz,
+                                    C.POINTER(u32)], i32),
+        "aqz_reader_region_chunks": ([vp, u32, u32, C.POINTER(RegionC), vp, sz,
+                                      C.POINTER(u32)], i32),
+        "aqz_reader_load_frames_region": ([vp, vp, sz, i32, vp, vp, u32, i32, u32, u32,
+                                           C.POINTER(RegionC), vp], i32),
+        "aqz_reader_read_region": ([vp, u32, u32, C.POINTER(RegionC), vp, u64, u64, vp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -451,6 +477,13 @@ class Dims:
                                                row_end, chunk0, dst.ctypes.data, dst.nbytes,
                                                has_data.ctypes.data, has_data.size),
                "aqz_dims_split_frame_rows")
+
+    def region_chunks(self, first, count, region):
+        """aqz_dims_region_chunks: the chunks of a layer (ascending, uint32) that
+        hold a pixel of region = (x0, y0, width, height) in layer-local frames
+        [first, first + count)."""
+        return _region_chunks(lib().aqz_dims_region_chunks, self.h, "aqz_dims_region_chunks",
+                              first, count, region)
 
     def dim1_banding(self):
         """(supported, n_bands, frames_per_band, chunks_per_band)"""
@@ -993,6 +1026,8 @@ class Compressor:
 DECODE_OK, DECODE_SKIPPED, DECODE_BAD_HEADER, DECODE_CORRUPT, DECODE_UNSUPPORTED = range(5)
 AQZ_DECODE_OK, AQZ_DECODE_SKIPPED, AQZ_DECODE_BAD_HEADER = DECODE_OK, DECODE_SKIPPED, DECODE_BAD_HEADER
 AQZ_DECODE_CORRUPT, AQZ_DECODE_UNSUPPORTED = DECODE_CORRUPT, DECODE_UNSUPPORTED
+# after Reader.load_frames_region: the chunk lies outside the loaded window
+DECODE_NOT_LOADED = AQZ_DECODE_NOT_LOADED = 5
 DECODE_CODEC_LZ4, DECODE_CODEC_ZSTD = 1, 2
 AQZ_DECODE_CODEC_LZ4, AQZ_DECODE_CODEC_ZSTD = DECODE_CODEC_LZ4, DECODE_CODEC_ZSTD
 # option bit of a codecs mask, with DECODE_CODEC_ZSTD only: plain zstd frames
@@ -1166,6 +1201,42 @@ class Reader:
     def read_frames_ptr(self, first, count, dst_ptr, dst_stride, stream_ptr=None):
         _check(lib().aqz_reader_read_frames(self.h, first, count, dst_ptr, dst_stride,
                                             stream_ptr), "aqz_reader_read_frames")
+
+    def region_chunks(self, first, count, region):
+        """Dims.region_chunks for the reader's own dims."""
+        return _region_chunks(lib().aqz_reader_region_chunks, self.h,
+                              "aqz_reader_region_chunks", first, count, region)
+
+    def load_frames_region(self, frames, offsets, first, count, region, chunk_of_frame=None,
+                           codec=CODEC_BLOSC_LZ4, frames_bytes=None, stream_ptr=None):
+        """load_frames for the window (first, count, region) only: frames of
+        chunks outside region_chunks(first, count, region) are neither copied
+        nor decoded nor read, and their status is DECODE_NOT_LOADED."""
+        if isinstance(frames, tuple):
+            p, mem = frames
+        else:
+            p, mem = _ptr(frames)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(off) - 1
+        if frames_bytes is None:
+            frames_bytes = int(off[-1])
+        cof = None
+        if chunk_of_frame is not None:
+            cof = np.ascontiguousarray(chunk_of_frame, dtype=np.uint32)
+            assert len(cof) == n
+        _check(lib().aqz_reader_load_frames_region(
+            self.h, p, frames_bytes, mem, off.ctypes.data,
+            cof.ctypes.data if cof is not None else None, n, codec, first, count,
+            _region(region), stream_ptr), "aqz_reader_load_frames_region")
+        self._held = frames
+
+    def read_region_ptr(self, first, count, region, dst_ptr, dst_row_stride, dst_frame_stride,
+                        stream_ptr=None):
+        """Pixel (y0 + j, x0 + i) of frame first + k -> dst_ptr + k *
+        dst_frame_stride + j * dst_row_stride + i * bytes per pixel."""
+        _check(lib().aqz_reader_read_region(self.h, first, count, _region(region), dst_ptr,
+                                            dst_row_stride, dst_frame_stride, stream_ptr),
+               "aqz_reader_read_region")
 
     def status(self):
         """(per-chunk DECODE_* by chunk index, n_bad) of the last load; waits."""

@@ -6,6 +6,8 @@
 #include "aqz_engine.hh"
 #include "aqz_reader.hh"
 
+#include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <string>
@@ -1165,7 +1167,8 @@ aqz_compressor_run(aqz_compressor* c, const void* chunks, uint64_t pitch,
 static_assert(AQZ_DECODE_OK == dec::kOk && AQZ_DECODE_SKIPPED == dec::kSkipped &&
                 AQZ_DECODE_BAD_HEADER == dec::kBadHeader &&
                 AQZ_DECODE_CORRUPT == dec::kCorrupt &&
-                AQZ_DECODE_UNSUPPORTED == dec::kUnsupported,
+                AQZ_DECODE_UNSUPPORTED == dec::kUnsupported &&
+                AQZ_DECODE_NOT_LOADED > dec::kUnsupported,
               "decode status values");
 
 aqz_status
@@ -1436,6 +1439,79 @@ aqz_reader_read_frames(aqz_reader* r, uint32_t first, uint32_t count, void* dst,
 {
     return guard_sticky(r, [&] {
         r->r->read_frames(first, count, dst, dst_stride, static_cast<hipStream_t>(stream));
+    });
+}
+
+// ---- region reads ----------------------------------------------------------
+static_assert(sizeof(aqz_region) == sizeof(RegionArg) &&
+                offsetof(aqz_region, height) == offsetof(RegionArg, height),
+              "aqz_region layout");
+
+static const RegionArg*
+to_region(const aqz_region* region)
+{
+    return reinterpret_cast<const RegionArg*>(region);
+}
+
+static void
+put_chunks(const std::vector<uint32_t>& v, uint32_t* chunks, size_t cap, uint32_t* n)
+{
+    *n = uint32_t(v.size());
+    if (!chunks)
+        return;
+    if (cap < v.size())
+        throw Error(AQZ_STATUS_OVERFLOW, "chunks array below the region's chunk count");
+    std::copy(v.begin(), v.end(), chunks);
+}
+
+aqz_status
+aqz_dims_region_chunks(const aqz_dims* d, uint32_t first, uint32_t count,
+                       const aqz_region* region, uint32_t* chunks, size_t cap, uint32_t* n)
+{
+    if (n)
+        *n = 0;
+    return guard([&] {
+        if (!d || !d->ad || !region || !n)
+            throw Error(AQZ_STATUS_INVALID_ARGUMENT, "null dims, region or n");
+        put_chunks(region_chunks(*d->ad, first, count, to_region(region)), chunks, cap, n);
+    });
+}
+
+aqz_status
+aqz_reader_region_chunks(const aqz_reader* r, uint32_t first, uint32_t count,
+                         const aqz_region* region, uint32_t* chunks, size_t cap, uint32_t* n)
+{
+    if (n)
+        *n = 0;
+    return guard([&] {
+        if (!r || !r->r || !region || !n)
+            throw Error(AQZ_STATUS_INVALID_ARGUMENT, "null reader, region or n");
+        put_chunks(r->r->region_chunks(first, count, to_region(region)), chunks, cap, n);
+    });
+}
+
+aqz_status
+aqz_reader_load_frames_region(aqz_reader* r, const void* frames, size_t frames_bytes,
+                              int32_t mem, const uint64_t* offsets,
+                              const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
+                              uint32_t first, uint32_t count, const aqz_region* region,
+                              void* stream)
+{
+    return guard_sticky(r, [&] {
+        r->r->load_frames_region(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames,
+                                 codec, first, count, to_region(region),
+                                 static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_reader_read_region(aqz_reader* r, uint32_t first, uint32_t count, const aqz_region* region,
+                       void* dst, uint64_t dst_row_stride, uint64_t dst_frame_stride,
+                       void* stream)
+{
+    return guard_sticky(r, [&] {
+        r->r->read_region(first, count, to_region(region), dst, dst_row_stride,
+                          dst_frame_stride, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -4,12 +4,15 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 namespace aqz {
 
 namespace {
 
 constexpr int kMemHost = 0, kMemDevice = 1, kMemHostPinned = 2;
+// AQZ_DECODE_NOT_LOADED: a chunk outside the window of a region load
+constexpr uint32_t kNotLoaded = 5;
 
 uint64_t
 round16(uint64_t n)
@@ -89,22 +92,13 @@ Reader::Reader(const ReaderDesc& d)
 {
     ad_ = std::make_unique<ArrayDimensions>(d.dims, d.dtype, d.storage_order);
     const Sizes s = sizes(d, *ad_);
-    g_.W = ad_->width_dim().array_size_px;
-    g_.H = ad_->height_dim().array_size_px;
-    g_.tw = ad_->width_dim().chunk_size_px;
-    g_.th = ad_->height_dim().chunk_size_px;
-    g_.ntx = parts_along(g_.W, g_.tw);
-    g_.nty = parts_along(g_.H, g_.th);
-    g_.bpp = uint32_t(bytes_of_type(d.dtype));
-    g_.n_chunks = s.n;
-    g_.n_frames = s.F;
-    g_.xy = ad_->needs_xy_transposition() ? 1 : 0;
-    g_.bpc = ad_->bytes_per_chunk();
+    g_ = unsplit_geom(*ad_);
 
     // the stage's per-frame tables (aqz_engine.cpp, Stage::Stage), with the
     // chunk's own offset instead of a ring pitch folded in
     std::vector<uint64_t> tab_off(s.F);
-    std::vector<uint32_t> tab_grp(s.F);
+    std::vector<uint32_t>& tab_grp = h_tab_grp_;
+    tab_grp.resize(s.F);
     for (uint32_t f = 0; f < s.F; ++f) {
         const uint64_t sf = ad_->transpose_frame_id(f);
         tab_grp[f] = ad_->tile_group_offset(sf);
@@ -207,6 +201,39 @@ Reader::load_frames(const void* frames, size_t frames_bytes, int mem, const uint
                     const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
                     hipStream_t stream)
 {
+    load(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec, nullptr, stream);
+    windowed_ = false;
+}
+
+void
+Reader::load_frames_region(const void* frames, size_t frames_bytes, int mem,
+                           const uint64_t* offsets, const uint32_t* chunk_of_frame,
+                           uint32_t n_frames, int32_t codec, uint32_t first, uint32_t count,
+                           const RegionArg* region, hipStream_t stream)
+{
+    std::vector<uint8_t> window(g_.n_chunks, 0);
+    for (uint32_t c : region_chunks(first, count, region))
+        window[c] = 1;
+    load(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec, window.data(),
+         stream);
+    window_.swap(window);
+    window_first_ = first;
+    window_count_ = count;
+    window_region_ = *region;
+    windowed_ = true;
+}
+
+// With a window, the frames of chunks outside it are dropped here: they take
+// no decoder position of their own, nothing of them is copied and their bytes
+// are never addressed.  The frames that are needed are packed back to back
+// into the staging buffer (runs of adjacent frames in one copy each) whenever
+// the decoder runs or the frames lie in host memory; stored chunks in device
+// memory are borrowed where they lie.
+void
+Reader::load(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
+             const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
+             const uint8_t* window, hipStream_t stream)
+{
     const uint32_t n = g_.n_chunks;
     const uint32_t fam = family_of(codec);
     if (fam == ~0u)
@@ -235,12 +262,28 @@ Reader::load_frames(const void* frames, size_t frames_bytes, int mem, const uint
             throw Error(1, "chunk_of_frame lists a chunk twice");
         seen[order[q]] = 1;
     }
-    if (mem != kMemDevice && frames_bytes > staging_.n)
+    const bool pack = window && (mem != kMemDevice || fam);
+    if (pack) {
+        uint64_t needed = 0;
+        for (uint32_t q = 0; q < n_frames; ++q)
+            if (window[order[q]])
+                needed += offsets[q + 1] - offsets[q];
+        if (needed > staging_.n)
+            throw Error(1, mem == kMemDevice
+                             ? "the needed frames' bytes above the reader's max_frames_bytes "
+                               "(compressed frames in device memory are packed into the "
+                               "staging buffer for a region load too)"
+                             : "the needed frames' bytes above the reader's max_frames_bytes");
+    } else if (mem != kMemDevice && frames_bytes > staging_.n) {
         throw Error(1, "frames_bytes above the reader's max_frames_bytes");
+    }
 
     begin_load(stream);
-    const uint8_t* dframes = static_cast<const uint8_t*>(frames);
-    if (mem != kMemDevice) {
+    const uint8_t* given = static_cast<const uint8_t*>(frames);
+    const uint8_t* dframes = given;
+    if (pack) {
+        dframes = staging_.p;
+    } else if (mem != kMemDevice) {
         if (frames_bytes)
             hip_check(hipMemcpyAsync(staging_.p, frames, frames_bytes, hipMemcpyHostToDevice,
                                      stream),
@@ -250,34 +293,65 @@ Reader::load_frames(const void* frames, size_t frames_bytes, int mem, const uint
     for (uint32_t c = 0; c < n; ++c)
         h_chunk_src_[c] = unsplit::kNoChunk;
     std::fill(chunk_status_.begin(), chunk_status_.end(), uint32_t(dec::kSkipped));
+    // the pending copy of a run of adjacent needed frames (pack only)
+    const hipMemcpyKind kind =
+      mem == kMemDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    uint64_t run_src = 0, run_dst = 0, run_len = 0, packed = 0;
+    auto flush = [&] {
+        if (run_len)
+            hip_check(hipMemcpyAsync(staging_.p + run_dst, given + run_src, run_len, kind,
+                                     stream),
+                      "hipMemcpyAsync");
+        run_len = 0;
+    };
     uint64_t align = 0;
+    uint32_t slot = 0; // decoder positions taken so far; q itself without a window
     for (uint32_t q = 0; q < n_frames; ++q) {
         const uint64_t len = offsets[q + 1] - offsets[q];
         const uint32_t c = order[q];
-        h_offsets_[q] = offsets[q];
-        h_order_[q] = c;
+        if (window && !window[c]) {
+            seen[c] = 0; // follows below as a zero-length frame, like a chunk not listed
+            continue;
+        }
+        const uint64_t at = pack ? packed : offsets[q];
+        h_offsets_[slot] = at;
+        h_order_[slot++] = c;
         if (len == 0)
             continue;
+        if (pack) {
+            if (run_len && offsets[q] == run_src + run_len) {
+                run_len += len;
+            } else {
+                flush();
+                run_src = offsets[q];
+                run_dst = packed;
+                run_len = len;
+            }
+            packed += len;
+        }
         if (fam) {
             h_chunk_src_[c] = c * layer_pitch_;
         } else if (len == g_.bpc) {
             // a stored chunk is its own frame
-            h_chunk_src_[c] = offsets[q];
-            align |= offsets[q];
+            h_chunk_src_[c] = at;
+            align |= at;
             chunk_status_[c] = dec::kOk;
         } else {
             chunk_status_[c] = dec::kBadHeader;
         }
     }
+    flush();
     // the decoder takes a permutation of the layer's chunks (a slot per frame
     // of the run): the chunks not listed follow as zero-length frames
-    uint32_t fill = n_frames;
+    const uint64_t end = pack ? packed : offsets[n_frames];
+    const uint64_t dec_bytes = pack ? packed : frames_bytes;
+    uint32_t fill = slot;
     for (uint32_t c = 0; c < n && fill < n; ++c)
         if (!seen[c]) {
-            h_offsets_[fill] = offsets[n_frames];
+            h_offsets_[fill] = end;
             h_order_[fill++] = c;
         }
-    h_offsets_[n] = offsets[n_frames];
+    h_offsets_[n] = end;
     // [chunk_src][offsets] lie back to back on both sides
     hip_check(hipMemcpyAsync(d_chunk_src_, h_chunk_src_, size_t(n) * 8 + (size_t(n) + 1) * 8,
                              hipMemcpyHostToDevice, stream),
@@ -286,8 +360,8 @@ Reader::load_frames(const void* frames, size_t frames_bytes, int mem, const uint
         hip_check(hipMemcpyAsync(d_order_, h_order_, size_t(n) * 4, hipMemcpyHostToDevice,
                                  stream),
                   "hipMemcpyAsync");
-        dec_->run(dframes, frames_bytes, d_offsets_, n, layer_.p, layer_pitch_, g_.bpc,
-                  d_status_, stream, d_order_);
+        dec_->run(dframes, dec_bytes, d_offsets_, n, layer_.p, layer_pitch_, g_.bpc, d_status_,
+                  stream, d_order_);
         hip_check(hipMemcpyAsync(h_status_, d_status_, size_t(n) * 4, hipMemcpyDeviceToHost,
                                  stream),
                   "hipMemcpyAsync");
@@ -320,6 +394,7 @@ Reader::load_chunks(const void* chunks, uint64_t pitch, const uint32_t* has_data
     src_ = static_cast<const uint8_t*>(chunks);
     src_align_ = uint64_t(reinterpret_cast<uintptr_t>(chunks)) | pitch;
     loaded_ = Loaded::Chunks;
+    windowed_ = false;
 }
 
 void
@@ -336,6 +411,12 @@ Reader::read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stri
         throw Error(1, "null destination");
     if (dst_stride < unsplit::frame_bytes(g_))
         throw Error(1, "dst_stride below the frame size");
+    if (windowed_) {
+        unsplit::Region whole;
+        unsplit::make_region(g_, 0, 0, g_.xy ? g_.H : g_.W, g_.xy ? g_.W : g_.H,
+                             uint64_t(g_.xy ? g_.H : g_.W) * g_.bpp, whole);
+        check_window(first, count, whole);
+    }
     unsplit::Params p{};
     p.g = g_;
     p.src = src_;
@@ -350,6 +431,74 @@ Reader::read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stri
     hip_check(hipStreamWaitEvent(stream, load_ev_, 0), "hipStreamWaitEvent");
     const uint64_t align = src_align_ | uint64_t(reinterpret_cast<uintptr_t>(dst)) | dst_stride;
     hip_check(launch_unsplit(p, align, stream), "unsplit launch");
+    hip_check(hipEventRecord(read_ev_, stream), "hipEventRecord");
+    read_pending_ = true;
+}
+
+void
+Reader::check_window(uint32_t first, uint32_t count, const unsplit::Region& R) const
+{
+    std::vector<uint8_t> mark(g_.n_chunks, 0);
+    for (uint32_t f = first; f < first + count; ++f)
+        if (!unsplit::region_mark_chunks(g_, R, h_tab_grp_[f], mark.data()))
+            throw Error(9, "the frame tables leave the layer");
+    for (uint32_t c = 0; c < g_.n_chunks; ++c)
+        if (mark[c] && !window_[c])
+            throw Error(1, "the read needs chunk " + std::to_string(c) +
+                             ", outside the loaded window: frames [" +
+                             std::to_string(window_first_) + ", " +
+                             std::to_string(uint64_t(window_first_) + window_count_) +
+                             "), region x0 " + std::to_string(window_region_.x0) + " y0 " +
+                             std::to_string(window_region_.y0) + " width " +
+                             std::to_string(window_region_.width) + " height " +
+                             std::to_string(window_region_.height));
+}
+
+std::vector<uint32_t>
+Reader::region_chunks(uint32_t first, uint32_t count, const RegionArg* region) const
+{
+    return aqz::region_chunks(*ad_, first, count, region);
+}
+
+void
+Reader::read_region(uint32_t first, uint32_t count, const RegionArg* region, void* dst,
+                    uint64_t dst_row_stride, uint64_t dst_frame_stride, hipStream_t stream)
+{
+    if (loaded_ == Loaded::None)
+        throw Error(1, "no layer loaded");
+    if (!region)
+        throw Error(1, "null region");
+    if (count == 0 || uint64_t(first) + count > g_.n_frames)
+        throw Error(1, "frame range empty or outside the layer");
+    unsplit::RegionParams q{};
+    if (!unsplit::make_region(g_, region->x0, region->y0, region->width, region->height,
+                              dst_row_stride, q.r)) {
+        unsplit::Region probe;
+        if (!unsplit::make_region(g_, region->x0, region->y0, region->width, region->height,
+                                  ~uint64_t(0), probe))
+            throw Error(1, "region empty or outside the frame");
+        throw Error(1, "dst_row_stride below the region's row bytes");
+    }
+    if (!dst)
+        throw Error(1, "null destination");
+    if (dst_frame_stride < unsplit::region_frame_extent(g_, q.r))
+        throw Error(1, "dst_frame_stride below the region's frame extent");
+    if (windowed_)
+        check_window(first, count, q.r);
+    q.p.g = g_;
+    q.p.src = src_;
+    q.p.chunk_src = d_chunk_src_;
+    q.p.tab_grp = d_tab_grp_;
+    q.p.tab_off = d_tab_off_;
+    q.p.dst = static_cast<uint8_t*>(dst);
+    q.p.dst_stride = dst_frame_stride;
+    q.p.first = first;
+    q.p.count = count;
+    // the load may have been enqueued on another stream
+    hip_check(hipStreamWaitEvent(stream, load_ev_, 0), "hipStreamWaitEvent");
+    const uint64_t align = src_align_ | uint64_t(reinterpret_cast<uintptr_t>(dst)) |
+                           dst_row_stride | dst_frame_stride;
+    hip_check(launch_unsplit_region(q, align, stream), "unsplit region launch");
     hip_check(hipEventRecord(read_ev_, stream), "hipEventRecord");
     read_pending_ = true;
 }
@@ -373,9 +522,11 @@ Reader::status(uint32_t* status, size_t cap, uint32_t* n_bad)
     }
     uint32_t bad = 0;
     for (uint32_t c = 0; c < n; ++c) {
+        // a chunk outside the window of a region load was not looked at
+        const uint32_t st = windowed_ && !window_[c] ? kNotLoaded : chunk_status_[c];
         if (status)
-            status[c] = chunk_status_[c];
-        bad += chunk_status_[c] > dec::kSkipped;
+            status[c] = st;
+        bad += st > dec::kSkipped && st != kNotLoaded;
     }
     if (n_bad)
         *n_bad = bad;

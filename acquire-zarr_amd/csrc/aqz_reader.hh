@@ -8,12 +8,16 @@
 #pragma once
 
 #include "aqz_engine.hh"
+#include "aqz_region.hh"
 #include "aqz_unsplit.hh"
 
 namespace aqz {
 
 // aqz_unsplit.hip.  align: see unsplit::copy_unit.
 hipError_t launch_unsplit(const unsplit::Params& p, uint64_t align, hipStream_t stream);
+// the crop of q.r; align as above plus the destination's frame stride
+hipError_t launch_unsplit_region(const unsplit::RegionParams& q, uint64_t align,
+                                 hipStream_t stream);
 hipError_t launch_chunk_table(uint64_t* chunk_src, uint32_t n, uint64_t pitch,
                               const uint32_t* has_data, uint32_t tag, hipStream_t stream);
 
@@ -46,10 +50,22 @@ class Reader
     void load_frames(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
                      const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
                      hipStream_t stream);
+    // load_frames for the window (first, count, region) only: frames of other
+    // chunks are neither copied nor decoded, and their bytes are not read
+    void load_frames_region(const void* frames, size_t frames_bytes, int mem,
+                            const uint64_t* offsets, const uint32_t* chunk_of_frame,
+                            uint32_t n_frames, int32_t codec, uint32_t first, uint32_t count,
+                            const RegionArg* region, hipStream_t stream);
     void load_chunks(const void* chunks, uint64_t pitch, const uint32_t* has_data, uint32_t tag,
                      hipStream_t stream);
     void read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stride,
                      hipStream_t stream);
+    // the crop of frames [first, first + count): pixel (y0 + j, x0 + i) of frame
+    // first + k -> dst + k * dst_frame_stride + j * dst_row_stride + i * bpp
+    void read_region(uint32_t first, uint32_t count, const RegionArg* region, void* dst,
+                     uint64_t dst_row_stride, uint64_t dst_frame_stride, hipStream_t stream);
+    std::vector<uint32_t> region_chunks(uint32_t first, uint32_t count,
+                                        const RegionArg* region) const;
     // waits for the last load; status[c] of chunk c, *n_bad = error statuses
     void status(uint32_t* status, size_t cap, uint32_t* n_bad);
 
@@ -57,12 +73,19 @@ class Reader
     struct Sizes;
     static Sizes sizes(const ReaderDesc& d, const ArrayDimensions& ad);
     void begin_load(hipStream_t stream);
+    // window: per chunk, 1 = inside the loaded window; nullptr = the whole layer
+    void load(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
+              const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
+              const uint8_t* window, hipStream_t stream);
+    // a read of these frames of this region stays inside the loaded window
+    void check_window(uint32_t first, uint32_t count, const unsplit::Region& R) const;
 
     int32_t device_;
     uint32_t codecs_;
     std::unique_ptr<ArrayDimensions> ad_;
     unsplit::Geom g_{};
     std::vector<uint32_t> shard_order_; // position -> chunk, as compress_layer writes
+    std::vector<uint32_t> h_tab_grp_;   // host copy of tab_grp: the chunk sets of regions
     // one device block: [tab_off F u64][chunk_src n u64][offsets n+1 u64]
     // [tab_grp F u32][order n u32][status n u32]
     DevBuf tables_;
@@ -94,6 +117,12 @@ class Reader
     const uint8_t* src_ = nullptr;
     uint64_t src_align_ = 0;
     std::vector<uint32_t> chunk_status_;
+    // the window of the last load_frames_region (host memory only): the chunks
+    // it loaded, and its description for the error text
+    bool windowed_ = false;
+    std::vector<uint8_t> window_;
+    uint32_t window_first_ = 0, window_count_ = 0;
+    RegionArg window_region_{};
     hipEvent_t load_ev_ = nullptr; // the last load has run
     hipEvent_t read_ev_ = nullptr; // the last read has run
     bool read_pending_ = false;

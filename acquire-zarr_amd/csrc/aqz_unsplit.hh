@@ -206,5 +206,250 @@ struct Params
     uint32_t first, count;
 };
 
+// ---- region reads ---------------------------------------------------------
+// A crop of frames: the same map, walked only over the tiles and slabs that
+// meet the region, each rectangle clipped to it and the destination rebased
+// to the region's origin with the caller's row pitch.
+//
+// The region in storage coordinates (make_region applies the XY swap once,
+// on the host, as Geom::xy is applied), with the ranges the walk needs.
+struct Region
+{
+    uint32_t x0, y0, w, h;     // storage columns [x0, x0 + w), rows [y0, y0 + h)
+    uint32_t tx0, ntx;         // tile columns tx0 .. tx0 + ntx - 1 meet it
+    uint32_t ty0, nty;         // tile rows ty0 .. ty0 + nty - 1 meet it
+    uint32_t s0;               // first slab of tile row ty0 that meets it
+    uint32_t n_first, n_last;  // slabs of the first / the last tile row that meet it
+    uint64_t row_pitch;        // bytes from destination row to destination row
+};
+
+// pixels per row and rows of the crop handed back (acquisition orientation)
+AQZ_HD inline uint32_t
+region_width(const Geom& g, const Region& R)
+{
+    return g.xy ? R.h : R.w;
+}
+
+AQZ_HD inline uint32_t
+region_height(const Geom& g, const Region& R)
+{
+    return g.xy ? R.w : R.h;
+}
+
+// bytes of one destination frame that a read may write: the last row is cut
+AQZ_HD inline uint64_t
+region_frame_extent(const Geom& g, const Region& R)
+{
+    return (uint64_t(region_height(g, R)) - 1) * R.row_pitch +
+           uint64_t(region_width(g, R)) * g.bpp;
+}
+
+AQZ_HD inline bool
+region_valid(const Geom& g, const Region& R)
+{
+    if (R.w == 0 || R.h == 0 || g.tw == 0 || g.th == 0 || g.bpp == 0)
+        return false;
+    if (uint64_t(R.x0) + R.w > g.W || uint64_t(R.y0) + R.h > g.H)
+        return false;
+    const uint32_t x1 = R.x0 + R.w - 1, y1 = R.y0 + R.h - 1;
+    if (R.tx0 != R.x0 / g.tw || R.ntx != x1 / g.tw - R.tx0 + 1)
+        return false;
+    if (R.ty0 != R.y0 / g.th || R.nty != y1 / g.th - R.ty0 + 1)
+        return false;
+    const uint32_t s0 = (R.y0 - R.ty0 * g.th) / kSlabRows;
+    const uint32_t s1 = (y1 - (R.ty0 + R.nty - 1) * g.th) / kSlabRows; // of the last tile row
+    if (R.s0 != s0 || R.n_last != s1 + 1 - (R.nty == 1 ? s0 : 0))
+        return false;
+    if (R.n_first != (R.nty == 1 ? R.n_last : slabs_per_tile(g) - s0))
+        return false;
+    return R.row_pitch >= uint64_t(region_width(g, R)) * g.bpp;
+}
+
+// The region (x0, y0, width, height) in pixels of the frames handed back
+// (acquisition orientation) -> storage coordinates and walk ranges.  False
+// when it is empty or leaves the frame; the sums are taken in 64 bits.
+inline bool
+make_region(const Geom& g, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+            uint64_t row_pitch, Region& R)
+{
+    R = Region{};
+    if (g.xy) {
+        R.x0 = y0, R.w = height;
+        R.y0 = x0, R.h = width;
+    } else {
+        R.x0 = x0, R.w = width;
+        R.y0 = y0, R.h = height;
+    }
+    if (R.w == 0 || R.h == 0 || g.tw == 0 || g.th == 0 || g.bpp == 0)
+        return false;
+    if (uint64_t(R.x0) + R.w > g.W || uint64_t(R.y0) + R.h > g.H)
+        return false;
+    const uint32_t x1 = R.x0 + R.w - 1, y1 = R.y0 + R.h - 1;
+    R.tx0 = R.x0 / g.tw;
+    R.ntx = x1 / g.tw - R.tx0 + 1;
+    R.ty0 = R.y0 / g.th;
+    R.nty = y1 / g.th - R.ty0 + 1;
+    R.s0 = (R.y0 - R.ty0 * g.th) / kSlabRows;
+    const uint32_t s1 = (y1 - (R.ty0 + R.nty - 1) * g.th) / kSlabRows;
+    R.n_last = s1 + 1 - (R.nty == 1 ? R.s0 : 0);
+    R.n_first = R.nty == 1 ? R.n_last : slabs_per_tile(g) - R.s0;
+    R.row_pitch = row_pitch;
+    return region_valid(g, R);
+}
+
+// 64-row slabs of the region's tile rows, top to bottom
+AQZ_HD inline uint64_t
+region_slab_rows(const Geom& g, const Region& R)
+{
+    if (R.nty == 1)
+        return R.n_first;
+    return uint64_t(R.n_first) + uint64_t(R.nty - 2) * slabs_per_tile(g) + R.n_last;
+}
+
+// work items of one frame of the region: (slab row, tile column), the tile
+// column fastest
+AQZ_HD inline uint64_t
+region_items_per_frame(const Geom& g, const Region& R)
+{
+    return region_slab_rows(g, R) * R.ntx;
+}
+
+// tile_rect's rectangle clipped to the region; the destination is relative
+// to the crop's first byte.  kMove only when every source byte lies inside
+// [0, bpc) of a chunk below n_chunks and every destination byte inside the
+// width * bpp bytes of a row below height of the crop.
+AQZ_HD inline uint32_t
+region_rect(const Geom& g, const Region& R, uint32_t grp, uint64_t internal, uint32_t ty,
+            uint32_t tx, uint32_t slab, Rect& r)
+{
+    const uint32_t st = tile_rect(g, grp, internal, ty, tx, slab, r);
+    if (st != kMove)
+        return st;
+    if (R.row_pitch < uint64_t(region_width(g, R)) * g.bpp)
+        return kBad;
+    const uint64_t Y0 = uint64_t(ty) * g.th + uint64_t(slab) * kSlabRows;
+    const uint64_t X0 = uint64_t(tx) * g.tw;
+    const uint64_t ya = Y0 > R.y0 ? Y0 : R.y0, xa = X0 > R.x0 ? X0 : R.x0;
+    uint64_t yb = Y0 + r.rows, xb = X0 + r.cols;
+    if (yb > uint64_t(R.y0) + R.h)
+        yb = uint64_t(R.y0) + R.h;
+    if (xb > uint64_t(R.x0) + R.w)
+        xb = uint64_t(R.x0) + R.w;
+    if (yb <= ya || xb <= xa)
+        return kEmpty;
+    const uint64_t rows = yb - ya, cols = xb - xa;
+    r.src += (ya - Y0) * r.src_pitch + (xa - X0) * g.bpp;
+    r.rows = uint32_t(rows);
+    r.cols = uint32_t(cols);
+    if (r.src + (rows - 1) * r.src_pitch + cols * g.bpp > g.bpc)
+        return kBad;
+    const uint64_t ry = ya - R.y0, rx = xa - R.x0; // inside the region
+    if (ry + rows > R.h || rx + cols > R.w)
+        return kBad;
+    r.dst_pitch = R.row_pitch;
+    if (!g.xy) {
+        r.dst = ry * R.row_pitch + rx * g.bpp;
+        r.dst_rows = r.rows;
+        r.dst_row_bytes = cols * g.bpp;
+    } else {
+        // storage pixel (y, x) -> row x, pixel y of a crop of R.w rows of R.h
+        r.dst = rx * R.row_pitch + ry * g.bpp;
+        r.dst_rows = r.cols;
+        r.dst_row_bytes = rows * g.bpp;
+    }
+    if (r.dst + (uint64_t(r.dst_rows) - 1) * r.dst_pitch + r.dst_row_bytes >
+        region_frame_extent(g, R))
+        return kBad;
+    return kMove;
+}
+
+// (ty, slab) of slab row `j` (< region_slab_rows) of the region
+AQZ_HD inline void
+region_slab_row(const Geom& g, const Region& R, uint64_t j, uint32_t& ty, uint32_t& slab)
+{
+    if (j < R.n_first) {
+        ty = R.ty0;
+        slab = R.s0 + uint32_t(j);
+        return;
+    }
+    const uint64_t k = j - R.n_first;
+    const uint32_t spt = slabs_per_tile(g);
+    ty = R.ty0 + 1 + uint32_t(k / spt);
+    slab = uint32_t(k % spt);
+}
+
+// Work item `item` (< region_items_per_frame) of layer-local frame `frame`,
+// as unsplit_item: the mover holds the source and the crop of that frame.
+template<bool XY, class Mover>
+AQZ_HD inline uint32_t
+region_item(const Geom& g, const Region& R, const uint32_t* tab_grp, const uint64_t* tab_off,
+            const uint64_t* chunk_src, uint32_t frame, uint64_t item, Mover& m)
+{
+    // R is make_region's (the launch checks region_valid on the host); whatever
+    // it holds, region_rect bounds every byte by itself
+    if (frame >= g.n_frames || XY != (g.xy != 0) || R.ntx == 0 || g.th == 0 ||
+        item >= region_items_per_frame(g, R))
+        return kBad;
+    uint32_t ty, slab;
+    region_slab_row(g, R, item / R.ntx, ty, slab);
+    const uint32_t tx = R.tx0 + uint32_t(item % R.ntx);
+    Rect r;
+    const uint32_t st = region_rect(g, R, tab_grp[frame], tab_off[frame], ty, tx, slab, r);
+    if (st != kMove)
+        return st;
+    const uint64_t base = chunk_src[r.chunk];
+    if (base == kNoChunk)
+        m.zero(r);
+    else if constexpr (XY)
+        m.transpose(base, r);
+    else
+        m.copy(base, r);
+    return kMove;
+}
+
+// Host: mark[c] = 1 for every chunk that a read of frames [first, first +
+// count) of the region can touch -- the tile ranges of the walk above, so a
+// chunk the map can reach is always marked.  False when a chunk index leaves
+// the layer (geometry and table disagree).
+inline bool
+region_mark_chunks(const Geom& g, const Region& R, uint32_t grp, uint8_t* mark)
+{
+    for (uint32_t ty = R.ty0; ty < R.ty0 + R.nty; ++ty)
+        for (uint32_t tx = R.tx0; tx < R.tx0 + R.ntx; ++tx) {
+            const uint64_t c = uint64_t(grp) + uint64_t(ty) * g.ntx + tx;
+            if (c >= g.n_chunks)
+                return false;
+            mark[c] = 1;
+        }
+    return true;
+}
+
+// copy_unit for a crop: the clip edges x0 and x0 + w and the crop's row pitch
+// join the word; the frame's own row length does not (a rectangle is cut
+// either at a tile edge or at a region edge).  `align` also holds the
+// destination address and the destination frame stride.
+inline uint32_t
+region_copy_unit(const Geom& g, const Region& R, uint64_t align)
+{
+    const uint64_t a = align | uint64_t(g.tw) * g.bpp | uint64_t(R.x0) * g.bpp |
+                       uint64_t(R.w) * g.bpp | R.row_pitch | 16u;
+    return uint32_t(a & (~a + 1));
+}
+
+// XY path of a crop: may pixels be moved as words of bpp bytes?
+inline bool
+region_pixel_aligned(const Geom& g, const Region& R, uint64_t align)
+{
+    return pixel_aligned(g, align | R.row_pitch);
+}
+
+// One launch: the crop of frames [first, first + count) -> p.dst + i *
+// p.dst_stride, rows at r.row_pitch; p.dst_stride >= region_frame_extent
+struct RegionParams
+{
+    Params p;
+    Region r;
+};
+
 } // namespace unsplit
 } // namespace aqz

@@ -853,6 +853,68 @@ aqz_status aqz_reader_read_frames(aqz_reader* r, uint32_t first, uint32_t count,
  * chunks never written; *n_bad = chunks with an error status. */
 aqz_status aqz_reader_status(aqz_reader* r, uint32_t* status, size_t cap, uint32_t* n_bad);
 
+/* ---- region reads: a crop of a few frames, decoding only its chunks ---------
+ * A region is in pixels of the frames the reader hands back (acquisition
+ * orientation: the width / height of aqz_reader_layout).  It is valid when
+ * width > 0, height > 0, x0 + width <= layout.width and y0 + height <=
+ * layout.height, the sums taken in 64 bits. */
+typedef struct
+{
+    uint32_t x0, y0, width, height;
+} aqz_region;
+#define AQZ_DECODE_NOT_LOADED 5 /* aqz_reader_status after aqz_reader_load_frames_region: the
+                                   chunk lies outside the loaded window; not an error status */
+/* The chunks of a layer that hold a pixel of `region` in frames [first, first +
+ * count) (ids inside the layer, acquisition order, as aqz_reader_read_frames
+ * takes them): ascending, each once, through transpose_frame_id and an
+ * XY-swapped storage order of d.  Host only.  *n = the count needed, always;
+ * chunks == NULL: count only; cap < *n: AQZ_STATUS_OVERFLOW.
+ * AQZ_STATUS_INVALID_ARGUMENT (with an aqz_last_error text): an invalid
+ * region, count == 0, a range outside aqz_dims_frames_per_chunk_layer, NULL
+ * d, region or n. */
+aqz_status aqz_dims_region_chunks(const aqz_dims* d, uint32_t first, uint32_t count,
+                                  const aqz_region* region, uint32_t* chunks, size_t cap,
+                                  uint32_t* n);
+/* The same for a reader's own dims. */
+aqz_status aqz_reader_region_chunks(const aqz_reader* r, uint32_t first, uint32_t count,
+                                    const aqz_region* region, uint32_t* chunks, size_t cap,
+                                    uint32_t* n);
+/* aqz_reader_load_frames for the window (first, count, region) only; the
+ * arguments mean the same and the load is ordered the same way.  Frames of
+ * chunks outside aqz_reader_region_chunks(first, count, region) are neither
+ * copied to the device nor decoded, their bytes are not read (offsets is
+ * still checked whole), and their status is AQZ_DECODE_NOT_LOADED.  Chunks
+ * inside the window behave as after aqz_reader_load_frames: a zero-length
+ * frame or a chunk not listed is AQZ_DECODE_SKIPPED and reads as zeros.
+ * The needed frames are packed back to back into the reader's staging buffer,
+ * runs of adjacent frames in one copy each -- over PCIe for AQZ_MEM_HOST /
+ * AQZ_MEM_HOST_PINNED, on the device for AQZ_MEM_DEVICE with a codec (stored
+ * chunks, AQZ_CODEC_NONE, in device memory are borrowed where they lie) -- so
+ * the limit is the sum of the needed frames' bytes <= max_frames_bytes, not
+ * frames_bytes.  The reader remembers the window until the next load: a
+ * read_region or read_frames whose chunks are not all inside it is
+ * AQZ_STATUS_INVALID_ARGUMENT, the text names the window, and nothing is
+ * enqueued (a chunk that was not loaded never reads as zeros silently). */
+aqz_status aqz_reader_load_frames_region(aqz_reader* r, const void* frames, size_t frames_bytes,
+                                         int32_t mem, const uint64_t* offsets,
+                                         const uint32_t* chunk_of_frame, uint32_t n_frames,
+                                         int32_t codec, uint32_t first, uint32_t count,
+                                         const aqz_region* region, void* stream);
+/* The crop of frames [first, first + count) of the loaded layer, after any
+ * load: pixel (y0 + j, x0 + i) of frame first + k goes to dst + k *
+ * dst_frame_stride + j * dst_row_stride + i * bytes_per_pixel (device).  Only
+ * those width * bytes_per_pixel bytes of each of the height rows are written,
+ * so dst may be a window of a larger canvas.  dst_row_stride >= width * bpp,
+ * dst_frame_stride >= (height - 1) * dst_row_stride + width * bpp, any
+ * alignment (16-byte units when x0 * bpp, width * bpp, both strides and dst
+ * are multiples of 16, narrower ones otherwise).  Enqueued on `stream` behind
+ * the load.  AQZ_STATUS_INVALID_ARGUMENT: NULL or invalid region, count == 0
+ * or a range outside the layer, a stride too small, nothing loaded, chunks
+ * outside the window of a region load. */
+aqz_status aqz_reader_read_region(aqz_reader* r, uint32_t first, uint32_t count,
+                                  const aqz_region* region, void* dst, uint64_t dst_row_stride,
+                                  uint64_t dst_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
