@@ -321,7 +321,14 @@ aqz_status aqz_stage_wait_stream(aqz_stage* st, void* stream);
  *    asynchronously; keep the bytes unchanged until aqz_stage_frames_consumed
  *    counts them (or aqz_stage_synchronize returns).
  * The H2D runs on the stage's copy stream and overlaps earlier batches'
- * kernels and hand-off copies. */
+ * kernels and hand-off copies.
+ * Source address (AQZ_MEM_DEVICE): any address aligned to the pixel size is
+ * accepted and gives the same chunk layers.  A 16-byte-aligned address
+ * whose rows are a multiple of 16 bytes (for an XY-swapped storage order:
+ * the acquisition rows) takes the fast kernels; any other is read one pixel
+ * at a time by the bounds-checked edge kernel (2-D), the generic one-level
+ * cascade (2x2x2) or the separate transpose pass (XY), which are slower.
+ * Host sources are staged into 16-byte-aligned device buffers. */
 aqz_status aqz_stage_append(aqz_stage* st, const void* frames,
                             uint64_t n_frames, int32_t mem);
 aqz_status aqz_stage_synchronize(aqz_stage* st);
