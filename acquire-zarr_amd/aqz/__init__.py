@@ -167,6 +167,22 @@ def _region(region):
     return None if region is None else C.byref(RegionC(*region))
 
 
+class ByteRangeC(C.Structure):
+    """aqz_byte_range: chunk bytes [lo, hi)."""
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_uint64)]
+
+
+def _region_chunk_ranges(fn, h, what, first, count, region):
+    """(chunks uint32[n], ranges uint64[n, 2]) of a *_region_chunk_ranges call"""
+    n = C.c_uint32(0)
+    _check(fn(h, first, count, _region(region), None, None, 0, C.byref(n)), what)
+    chunks = np.empty(n.value, dtype=np.uint32)
+    ranges = np.empty((n.value, 2), dtype=np.uint64)
+    _check(fn(h, first, count, _region(region), chunks.ctypes.data, ranges.ctypes.data, n.value,
+              C.byref(n)), what)
+    return chunks, ranges
+
+
 def _region_chunks(fn, h, what, first, count, region):
     n = C.c_uint32(0)
     _check(fn(h, first, count, _region(region), None, 0, C.byref(n)), what)
@@ -342,6 +358,15 @@ def lib():
         "aqz_reader_load_frames_region": ([vp, vp, sz, i32, vp, vp, u32, i32, u32, u32,
                                            C.POINTER(RegionC), vp], i32),
         "aqz_reader_read_region": ([vp, u32, u32, C.POINTER(RegionC), vp, u64, u64, vp], i32),
+        "aqz_dims_region_chunk_ranges": ([vp, u32, u32, C.POINTER(RegionC), vp, vp, sz,
+                                          C.POINTER(u32)], i32),
+        "aqz_reader_region_chunk_ranges": ([vp, u32, u32, C.POINTER(RegionC), vp, vp, sz,
+                                            C.POINTER(u32)], i32),
+        "aqz_decompressor_run_ranges": ([vp, vp, sz, vp, u32, vp, u64, u64, vp, vp, vp, vp],
+                                        i32),
+        "aqz_reader_load_frames_window": ([vp, vp, sz, i32, vp, vp, u32, i32, u32, u32,
+                                           C.POINTER(RegionC), vp], i32),
+        "aqz_reader_load_stats": ([vp, C.POINTER(u64), C.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -484,6 +509,13 @@ class Dims:
         [first, first + count)."""
         return _region_chunks(lib().aqz_dims_region_chunks, self.h, "aqz_dims_region_chunks",
                               first, count, region)
+
+    def region_chunk_ranges(self, first, count, region):
+        """aqz_dims_region_chunk_ranges: (chunks, ranges) -- region_chunks and, per
+        chunk, the smallest interval [lo, hi) of chunk bytes (uint64[n, 2]) that
+        holds every byte a crop of the region from those frames reads."""
+        return _region_chunk_ranges(lib().aqz_dims_region_chunk_ranges, self.h,
+                                    "aqz_dims_region_chunk_ranges", first, count, region)
 
     def dim1_banding(self):
         """(supported, n_bands, frames_per_band, chunks_per_band)"""
@@ -1082,6 +1114,16 @@ class Decompressor:
                                           n_chunks, dst_ptr, pitch, chunk_bytes, status_ptr,
                                           stream_ptr), "aqz_decompressor_run")
 
+    def run_ranges_ptr(self, frames_ptr, frames_bytes, offsets_ptr, n_chunks, dst_ptr, pitch,
+                       chunk_bytes, ranges_ptr, spans_ptr, status_ptr, stream_ptr=None):
+        """run_ptr over chunk bytes ranges[i] = (lo, hi) of frame i only (device
+        uint64[n_chunks, 2]); spans (device, same shape, or None) gets what was
+        decoded: the block-aligned interval for a blosc1 frame."""
+        _check(lib().aqz_decompressor_run_ranges(self.h, frames_ptr, frames_bytes, offsets_ptr,
+                                                 n_chunks, dst_ptr, pitch, chunk_bytes,
+                                                 ranges_ptr, spans_ptr, status_ptr, stream_ptr),
+               "aqz_decompressor_run_ranges")
+
     def last_run_counts(self):
         """What the last run did with its zstd frames (aqz_decompressor_last_run_counts;
         waits for it): {"parallel_frames", "serial_frames", "blocks", "sequences"}.
@@ -1207,11 +1249,18 @@ class Reader:
         return _region_chunks(lib().aqz_reader_region_chunks, self.h,
                               "aqz_reader_region_chunks", first, count, region)
 
+    def region_chunk_ranges(self, first, count, region):
+        """Dims.region_chunk_ranges for the reader's own dims."""
+        return _region_chunk_ranges(lib().aqz_reader_region_chunk_ranges, self.h,
+                                    "aqz_reader_region_chunk_ranges", first, count, region)
+
     def load_frames_region(self, frames, offsets, first, count, region, chunk_of_frame=None,
-                           codec=CODEC_BLOSC_LZ4, frames_bytes=None, stream_ptr=None):
+                           codec=CODEC_BLOSC_LZ4, frames_bytes=None, stream_ptr=None,
+                           window=False):
         """load_frames for the window (first, count, region) only: frames of
         chunks outside region_chunks(first, count, region) are neither copied
-        nor decoded nor read, and their status is DECODE_NOT_LOADED."""
+        nor decoded nor read, and their status is DECODE_NOT_LOADED.
+        window=True is load_frames_window."""
         if isinstance(frames, tuple):
             p, mem = frames
         else:
@@ -1224,11 +1273,28 @@ class Reader:
         if chunk_of_frame is not None:
             cof = np.ascontiguousarray(chunk_of_frame, dtype=np.uint32)
             assert len(cof) == n
-        _check(lib().aqz_reader_load_frames_region(
-            self.h, p, frames_bytes, mem, off.ctypes.data,
-            cof.ctypes.data if cof is not None else None, n, codec, first, count,
-            _region(region), stream_ptr), "aqz_reader_load_frames_region")
+        fn, what = (lib().aqz_reader_load_frames_window, "aqz_reader_load_frames_window") \
+            if window else (lib().aqz_reader_load_frames_region, "aqz_reader_load_frames_region")
+        _check(fn(self.h, p, frames_bytes, mem, off.ctypes.data,
+                  cof.ctypes.data if cof is not None else None, n, codec, first, count,
+                  _region(region), stream_ptr), what)
         self._held = frames
+
+    def load_frames_window(self, frames, offsets, first, count, region, chunk_of_frame=None,
+                           codec=CODEC_BLOSC_LZ4, frames_bytes=None, stream_ptr=None):
+        """aqz_reader_load_frames_window: load_frames_region that decodes each chunk
+        of the window over the window's byte hull only (region_chunk_ranges) and
+        leaves the other chunks alone; reads are then held to the exact window."""
+        self.load_frames_region(frames, offsets, first, count, region, chunk_of_frame, codec,
+                                frames_bytes, stream_ptr, window=True)
+
+    def load_stats(self):
+        """(decoded_bytes, copied_bytes) of the last load (aqz_reader_load_stats;
+        waits): chunk bytes the decoder wrote, frame bytes copied into staging."""
+        d, c = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().aqz_reader_load_stats(self.h, C.byref(d), C.byref(c)),
+               "aqz_reader_load_stats")
+        return d.value, c.value
 
     def read_region_ptr(self, first, count, region, dst_ptr, dst_row_stride, dst_frame_stride,
                         stream_ptr=None):

@@ -1515,6 +1515,99 @@ aqz_reader_read_region(aqz_reader* r, uint32_t first, uint32_t count, const aqz_
     });
 }
 
+// ---- window loads -----------------------------------------------------------
+static_assert(sizeof(aqz_byte_range) == sizeof(dec::ByteRange) &&
+                offsetof(aqz_byte_range, hi) == offsetof(dec::ByteRange, hi),
+              "aqz_byte_range layout");
+
+static void
+put_chunk_ranges(const std::vector<ChunkRange>& v, uint32_t* chunks, aqz_byte_range* ranges,
+                 size_t cap, uint32_t* n)
+{
+    *n = uint32_t(v.size());
+    if (!chunks && !ranges)
+        return;
+    if (cap < v.size())
+        throw Error(AQZ_STATUS_OVERFLOW, "chunks array below the region's chunk count");
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (chunks)
+            chunks[i] = v[i].chunk;
+        if (ranges)
+            ranges[i] = aqz_byte_range{ v[i].lo, v[i].hi };
+    }
+}
+
+aqz_status
+aqz_dims_region_chunk_ranges(const aqz_dims* d, uint32_t first, uint32_t count,
+                             const aqz_region* region, uint32_t* chunks, aqz_byte_range* ranges,
+                             size_t cap, uint32_t* n)
+{
+    if (n)
+        *n = 0;
+    return guard([&] {
+        if (!d || !d->ad || !region || !n)
+            throw Error(AQZ_STATUS_INVALID_ARGUMENT, "null dims, region or n");
+        put_chunk_ranges(region_chunk_ranges(*d->ad, first, count, to_region(region)), chunks,
+                         ranges, cap, n);
+    });
+}
+
+aqz_status
+aqz_reader_region_chunk_ranges(const aqz_reader* r, uint32_t first, uint32_t count,
+                               const aqz_region* region, uint32_t* chunks,
+                               aqz_byte_range* ranges, size_t cap, uint32_t* n)
+{
+    if (n)
+        *n = 0;
+    return guard([&] {
+        if (!r || !r->r || !region || !n)
+            throw Error(AQZ_STATUS_INVALID_ARGUMENT, "null reader, region or n");
+        put_chunk_ranges(r->r->region_chunk_ranges(first, count, to_region(region)), chunks,
+                         ranges, cap, n);
+    });
+}
+
+aqz_status
+aqz_decompressor_run_ranges(aqz_decompressor* d, const void* frames, size_t frames_bytes,
+                            const uint64_t* offsets, uint32_t n_chunks, void* dst,
+                            uint64_t pitch, uint64_t chunk_bytes, const aqz_byte_range* ranges,
+                            aqz_byte_range* spans, uint32_t* status, void* stream)
+{
+    if (!d || !frames || !offsets || !dst || !status || !ranges)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    return guard_sticky(d, [&] {
+        d->d->run_ranges(static_cast<const uint8_t*>(frames), frames_bytes, offsets, n_chunks,
+                         static_cast<uint8_t*>(dst), pitch, chunk_bytes,
+                         reinterpret_cast<const dec::ByteRange*>(ranges),
+                         reinterpret_cast<dec::ByteRange*>(spans), status,
+                         static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_reader_load_frames_window(aqz_reader* r, const void* frames, size_t frames_bytes,
+                              int32_t mem, const uint64_t* offsets,
+                              const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
+                              uint32_t first, uint32_t count, const aqz_region* region,
+                              void* stream)
+{
+    return guard_sticky(r, [&] {
+        r->r->load_frames_window(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames,
+                                 codec, first, count, to_region(region),
+                                 static_cast<hipStream_t>(stream));
+    });
+}
+
+aqz_status
+aqz_reader_load_stats(aqz_reader* r, uint64_t* decoded_bytes, uint64_t* copied_bytes)
+{
+    if (decoded_bytes)
+        *decoded_bytes = 0;
+    if (copied_bytes)
+        *copied_bytes = 0;
+    return guard_sticky(r, [&] { r->r->load_stats(decoded_bytes, copied_bytes); });
+}
+
 aqz_status
 aqz_reader_status(aqz_reader* r, uint32_t* status, size_t cap, uint32_t* n_bad)
 {

@@ -78,6 +78,38 @@ uint64_t zstd_decode_lit_pitch(uint64_t max_chunk_bytes);
 // included) -- decoded; other frames are not touched.
 hipError_t launch_zstd_decode(const DecodeParams& p, hipStream_t stream);
 
+// ---- ranged decode: only the blosc blocks that meet a byte range ----------
+// A run of DecodeParams p (no compare mode) in which frame q is decoded over
+// chunk bytes ranges[q] only (dec::range_status, dec::blocks_of_range):
+//   blosc1 frames      only the blocks that meet the range are looked up in
+//                      bstarts, decoded and un-shuffled; the span is the
+//                      block-aligned interval of dec::blocks_of_range
+//   memcpyed frames,   only [lo, hi) is copied / zero-filled; the span is
+//   zero-length frames [lo, hi)
+//   plain zstd frames  decoded whole (matches reach across blocks); the span
+//                      is [0, chunk_bytes)
+//   an empty range     status dec::kNotLoaded, empty span, the frame is not
+//                      decoded; a reversed range or hi > chunk_bytes:
+//                      dec::kBadHeader, empty span
+// No byte of a chunk outside its span is written.
+struct RangedParams
+{
+    DecodeParams p;
+    const dec::ByteRange* ranges; // [n_chunks] by frame position (device)
+    dec::ByteRange* spans;        // [n_chunks] what was decoded; nullptr: not wanted
+};
+// Enqueue: status and spans cleared; the LZ4, memcpyed and zero-length frames
+// decoded over their ranges and the statuses of empty and bad ranges set for
+// frames of every family.  max_range_bytes: an upper bound of hi - lo over
+// the run that sizes the grid (the needed blocks of a chunk are dealt over
+// the workgroups by their own count); 0 = unknown, chunk_bytes.
+hipError_t launch_blosc_decode_ranged(const RangedParams& rp, uint64_t max_range_bytes,
+                                      hipStream_t stream);
+// Enqueue behind it (and behind launch_zstd_parallel, where in use): the zstd
+// frames of the run, as launch_zstd_decode.
+hipError_t launch_zstd_decode_ranged(const RangedParams& rp, uint64_t max_range_bytes,
+                                     hipStream_t stream);
+
 // The block-parallel path of plain zstd frames (AQZ_DECODE_ZSTD_PARALLEL).
 // Per chunk of up to max_chunk_bytes: a table of cap blocks, then the literal
 // area, then the records; pitch bytes in all.

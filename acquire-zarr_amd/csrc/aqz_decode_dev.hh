@@ -172,5 +172,26 @@ frame_ref(const DecodeParams& p, uint32_t q, FrameRef& r)
     return true;
 }
 
+// the span frame q of a ranged run was decoded over (written by one thread)
+__device__ __forceinline__ void
+put_span(const RangedParams& rp, uint32_t q, uint64_t lo, uint64_t hi)
+{
+    if (rp.spans) {
+        rp.spans[q].lo = lo;
+        rp.spans[q].hi = hi;
+    }
+}
+
+// Workgroups per chunk of a ranged run: one per kDecodeLdsBytes of the longest
+// range and one more for a range that straddles a group edge, `cap` at most.
+inline uint32_t
+ranged_passes(uint64_t chunk_bytes, uint64_t max_range_bytes, uint32_t cap)
+{
+    const uint64_t bytes =
+      max_range_bytes && max_range_bytes < chunk_bytes ? max_range_bytes : chunk_bytes;
+    const uint64_t passes = (bytes + kDecodeLdsBytes - 1) / kDecodeLdsBytes + 1;
+    return passes > cap ? cap : uint32_t(passes);
+}
+
 } // namespace
 } // namespace aqz

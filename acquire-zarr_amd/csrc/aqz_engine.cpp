@@ -2718,10 +2718,10 @@ Decompressor::scratch_bytes(uint64_t max_chunk_bytes, uint32_t max_chunks, bool 
     return n;
 }
 
-void
-Decompressor::run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
-                  uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
-                  uint32_t* status, hipStream_t stream, const uint32_t* order, uint32_t* bad)
+DecodeParams
+Decompressor::params(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                     uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+                     uint32_t* status, const uint32_t* order, uint32_t* bad) const
 {
     if (chunk_bytes == 0 || chunk_bytes > max_chunk_bytes_)
         throw Error(1, "chunk size above the decompressor's max_chunk_bytes");
@@ -2756,12 +2756,49 @@ Decompressor::run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* 
         p.zpar_rec_off = l.rec_off;
         p.zpar_cap = l.cap;
     }
+    return p;
+}
+
+void
+Decompressor::run(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                  uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+                  uint32_t* status, hipStream_t stream, const uint32_t* order, uint32_t* bad)
+{
+    const DecodeParams p = params(frames, frames_bytes, offsets, n_chunks, dst, pitch,
+                                  chunk_bytes, status, order, bad);
     // clears the status words and takes the LZ4, memcpyed and zero-length frames
     hip_check(launch_blosc_decode(p, stream), "blosc decode launch");
     if (zpar_.p) // plain zstd frames, ahead of the serial kernel that takes the rest
         hip_check(launch_zstd_parallel(p, stream), "zstd parallel decode launch");
     if (codecs_ & dec::kFamilyZstd)
         hip_check(launch_zstd_decode(p, stream), "zstd decode launch");
+    last_stream_ = stream;
+}
+
+void
+Decompressor::run_ranges(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                         uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+                         const dec::ByteRange* ranges, dec::ByteRange* spans, uint32_t* status,
+                         hipStream_t stream, const uint32_t* order, uint64_t max_range_bytes)
+{
+    if (!ranges)
+        throw Error(1, "null ranges");
+    RangedParams rp{};
+    rp.p = params(frames, frames_bytes, offsets, n_chunks, dst, pitch, chunk_bytes, status, order,
+                  nullptr);
+    rp.ranges = ranges;
+    rp.spans = spans;
+    // clears the status words and the spans, gives empty and bad ranges their
+    // status, and takes the LZ4, memcpyed and zero-length frames
+    hip_check(launch_blosc_decode_ranged(rp, max_range_bytes, stream),
+              "ranged blosc decode launch");
+    // plain zstd frames are decoded whole: the parallel kernels of a full run
+    // (they leave a frame whose status is already set alone)
+    if (zpar_.p)
+        hip_check(launch_zstd_parallel(rp.p, stream), "zstd parallel decode launch");
+    if (codecs_ & dec::kFamilyZstd)
+        hip_check(launch_zstd_decode_ranged(rp, max_range_bytes, stream),
+                  "ranged zstd decode launch");
     last_stream_ = stream;
 }
 

@@ -246,6 +246,15 @@ class Decompressor
              uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
              uint32_t* status, hipStream_t stream, const uint32_t* order = nullptr,
              uint32_t* bad = nullptr);
+    // run() over chunk bytes ranges[q] of frame q only (aqz_decode.hh,
+    // RangedParams): ranges and spans are device arrays of n_chunks entries,
+    // spans optional.  max_range_bytes: an upper bound of hi - lo over the
+    // run where the caller knows one (it sizes the grid), else 0.
+    void run_ranges(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                    uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+                    const dec::ByteRange* ranges, dec::ByteRange* spans, uint32_t* status,
+                    hipStream_t stream, const uint32_t* order = nullptr,
+                    uint64_t max_range_bytes = 0);
     uint64_t device_bytes() const { return scratch_.n + zlit_.n + zpar_.n; }
     uint32_t codecs() const { return codecs_; }
     // Waits for the last run; the four words of aqz_decode_counts (zeros from a
@@ -253,6 +262,10 @@ class Decompressor
     void last_run_counts(uint32_t (&counts)[4]);
 
   private:
+    // the arguments checked, and the decoder's scratch bound
+    DecodeParams params(const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                        uint32_t n_chunks, uint8_t* dst, uint64_t pitch, uint64_t chunk_bytes,
+                        uint32_t* status, const uint32_t* order, uint32_t* bad) const;
     uint64_t max_chunk_bytes_;
     uint32_t max_chunks_;
     uint32_t codecs_;

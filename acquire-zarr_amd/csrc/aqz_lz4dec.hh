@@ -34,6 +34,7 @@ enum : uint32_t
     kBadHeader = 2,
     kCorrupt = 3,
     kUnsupported = 4,
+    kNotLoaded = 5, // a ranged decode with an empty range: the frame was not looked at
 };
 
 constexpr uint32_t kZstdMagic = 0xFD2FB528u;
@@ -140,6 +141,56 @@ block_info(const FrameInfo& h, uint32_t j)
                        h.blocksize / h.typesize >= 128 && !leftover;
     b.ns = split ? h.typesize : 1;
     b.slen = b.bsize / b.ns;
+    return b;
+}
+
+// A partial decode.  Every block of a blosc1 frame is compressed and shuffled
+// on its own, so chunk bytes [lo, hi) need only the blocks that meet them.
+struct ByteRange
+{
+    uint64_t lo, hi; // chunk bytes [lo, hi)
+};
+
+// 0: chunk bytes [lo, hi) can be asked of a chunk of chunk_bytes; kNotLoaded:
+// the range is empty (nothing is decoded, the frame is not looked at);
+// kBadHeader: it is reversed or leaves the chunk.
+AQZ_HD inline uint32_t
+range_status(ByteRange r, uint64_t chunk_bytes)
+{
+    if (r.lo > r.hi || r.hi > chunk_bytes)
+        return kBadHeader;
+    return r.lo == r.hi ? kNotLoaded : kOk;
+}
+
+struct BlockRange
+{
+    uint32_t jlo, jhi; // blocks [jlo, jhi) of the frame
+    uint64_t lo, hi;   // the chunk bytes they decode to
+};
+
+// The blocks of a parsed (not memcpyed) frame that meet chunk bytes [lo, hi):
+// [lo / blocksize, ceil(hi / blocksize)) clipped to nblocks, and the span
+// they decode to, [jlo * blocksize, min(jhi * blocksize, nbytes)).  An empty
+// or reversed range, and one past the frame's last byte, give no block and an
+// empty span.  64-bit arithmetic throughout: blocksize may exceed nbytes, and
+// hi + blocksize may exceed 2^32.
+AQZ_HD inline BlockRange
+blocks_of_range(const FrameInfo& h, uint64_t lo, uint64_t hi)
+{
+    BlockRange b{ 0, 0, 0, 0 };
+    if (lo >= hi || lo >= h.nbytes || h.blocksize == 0 || h.nblocks == 0)
+        return b;
+    const uint64_t bs = h.blocksize;
+    uint64_t jlo = lo / bs;
+    uint64_t jhi = hi / bs + (hi % bs ? 1u : 0u);
+    if (jhi > h.nblocks)
+        jhi = h.nblocks;
+    if (jlo >= jhi)
+        return b;
+    b.jlo = uint32_t(jlo);
+    b.jhi = uint32_t(jhi);
+    b.lo = jlo * bs;
+    b.hi = jhi * bs < h.nbytes ? jhi * bs : uint64_t(h.nbytes);
     return b;
 }
 

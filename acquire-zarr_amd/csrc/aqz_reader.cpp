@@ -164,7 +164,7 @@ Reader::~Reader()
 uint64_t
 Reader::device_bytes() const
 {
-    return tables_.n + layer_.n + staging_.n + (dec_ ? dec_->device_bytes() : 0);
+    return tables_.n + layer_.n + staging_.n + d_ranges_.n + (dec_ ? dec_->device_bytes() : 0);
 }
 
 LevelLayout
@@ -201,8 +201,10 @@ Reader::load_frames(const void* frames, size_t frames_bytes, int mem, const uint
                     const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
                     hipStream_t stream)
 {
-    load(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec, nullptr, stream);
+    load(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec, nullptr, nullptr,
+         stream);
     windowed_ = false;
+    window_exact_ = false;
 }
 
 void
@@ -215,12 +217,37 @@ Reader::load_frames_region(const void* frames, size_t frames_bytes, int mem,
     for (uint32_t c : region_chunks(first, count, region))
         window[c] = 1;
     load(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec, window.data(),
-         stream);
+         nullptr, stream);
     window_.swap(window);
     window_first_ = first;
     window_count_ = count;
     window_region_ = *region;
     windowed_ = true;
+    window_exact_ = false;
+}
+
+void
+Reader::load_frames_window(const void* frames, size_t frames_bytes, int mem,
+                           const uint64_t* offsets, const uint32_t* chunk_of_frame,
+                           uint32_t n_frames, int32_t codec, uint32_t first, uint32_t count,
+                           const RegionArg* region, hipStream_t stream)
+{
+    const std::vector<ChunkRange> hull = region_chunk_ranges(first, count, region);
+    std::vector<uint8_t> window(g_.n_chunks, 0);
+    for (const ChunkRange& c : hull)
+        window[c.chunk] = 1;
+    if (!d_ranges_.p && codecs_) {
+        d_ranges_.alloc(size_t(g_.n_chunks) * 2 * sizeof(dec::ByteRange));
+        h_ranges_.alloc(size_t(g_.n_chunks) * 2 * sizeof(dec::ByteRange));
+    }
+    load(frames, frames_bytes, mem, offsets, chunk_of_frame, n_frames, codec, window.data(),
+         &hull, stream);
+    window_.swap(window);
+    window_first_ = first;
+    window_count_ = count;
+    window_region_ = *region;
+    windowed_ = true;
+    window_exact_ = true;
 }
 
 // With a window, the frames of chunks outside it are dropped here: they take
@@ -232,7 +259,7 @@ Reader::load_frames_region(const void* frames, size_t frames_bytes, int mem,
 void
 Reader::load(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
              const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
-             const uint8_t* window, hipStream_t stream)
+             const uint8_t* window, const std::vector<ChunkRange>* hull, hipStream_t stream)
 {
     const uint32_t n = g_.n_chunks;
     const uint32_t fam = family_of(codec);
@@ -360,8 +387,31 @@ Reader::load(const void* frames, size_t frames_bytes, int mem, const uint64_t* o
         hip_check(hipMemcpyAsync(d_order_, h_order_, size_t(n) * 4, hipMemcpyHostToDevice,
                                  stream),
                   "hipMemcpyAsync");
-        dec_->run(dframes, dec_bytes, d_offsets_, n, layer_.p, layer_pitch_, g_.bpc, d_status_,
-                  stream, d_order_);
+        if (hull) {
+            // by decoder position: the hull for a chunk of the window, nothing for the rest
+            dec::ByteRange* h_ranges = reinterpret_cast<dec::ByteRange*>(h_ranges_.p);
+            dec::ByteRange* d_ranges = reinterpret_cast<dec::ByteRange*>(d_ranges_.p);
+            std::vector<dec::ByteRange> by_chunk(n, dec::ByteRange{ 0, 0 });
+            uint64_t longest = 0;
+            for (const ChunkRange& c : *hull) {
+                by_chunk[c.chunk] = dec::ByteRange{ c.lo, c.hi };
+                longest = std::max(longest, c.hi - c.lo);
+            }
+            for (uint32_t q = 0; q < n; ++q)
+                h_ranges[q] = by_chunk[h_order_[q]];
+            hip_check(hipMemcpyAsync(d_ranges, h_ranges, size_t(n) * sizeof(dec::ByteRange),
+                                     hipMemcpyHostToDevice, stream),
+                      "hipMemcpyAsync");
+            dec_->run_ranges(dframes, dec_bytes, d_offsets_, n, layer_.p, layer_pitch_, g_.bpc,
+                             d_ranges, d_ranges + n, d_status_, stream, d_order_, longest);
+            hip_check(hipMemcpyAsync(h_ranges + n, d_ranges + n,
+                                     size_t(n) * sizeof(dec::ByteRange), hipMemcpyDeviceToHost,
+                                     stream),
+                      "hipMemcpyAsync");
+        } else {
+            dec_->run(dframes, dec_bytes, d_offsets_, n, layer_.p, layer_pitch_, g_.bpc,
+                      d_status_, stream, d_order_);
+        }
         hip_check(hipMemcpyAsync(h_status_, d_status_, size_t(n) * 4, hipMemcpyDeviceToHost,
                                  stream),
                   "hipMemcpyAsync");
@@ -374,6 +424,9 @@ Reader::load(const void* frames, size_t frames_bytes, int mem, const uint64_t* o
     hip_check(hipEventRecord(load_ev_, stream), "hipEventRecord");
     loaded_frames_ = n;
     loaded_ = fam ? Loaded::Decoded : Loaded::Raw;
+    ranged_ = fam && hull;
+    stat_decoded_ = fam ? uint64_t(n) * g_.bpc : 0;
+    stat_copied_ = pack ? packed : mem != kMemDevice ? frames_bytes : 0;
 }
 
 void
@@ -395,6 +448,9 @@ Reader::load_chunks(const void* chunks, uint64_t pitch, const uint32_t* has_data
     src_align_ = uint64_t(reinterpret_cast<uintptr_t>(chunks)) | pitch;
     loaded_ = Loaded::Chunks;
     windowed_ = false;
+    window_exact_ = false;
+    ranged_ = false;
+    stat_decoded_ = stat_copied_ = 0;
 }
 
 void
@@ -415,7 +471,8 @@ Reader::read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stri
         unsplit::Region whole;
         unsplit::make_region(g_, 0, 0, g_.xy ? g_.H : g_.W, g_.xy ? g_.W : g_.H,
                              uint64_t(g_.xy ? g_.H : g_.W) * g_.bpp, whole);
-        check_window(first, count, whole);
+        check_window(first, count, whole,
+                     RegionArg{ 0, 0, g_.xy ? g_.H : g_.W, g_.xy ? g_.W : g_.H });
     }
     unsplit::Params p{};
     p.g = g_;
@@ -436,22 +493,70 @@ Reader::read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stri
 }
 
 void
-Reader::check_window(uint32_t first, uint32_t count, const unsplit::Region& R) const
+Reader::refuse_read(const std::string& what) const
 {
+    throw Error(1, what + ", outside the loaded window: frames [" +
+                     std::to_string(window_first_) + ", " +
+                     std::to_string(uint64_t(window_first_) + window_count_) + "), region x0 " +
+                     std::to_string(window_region_.x0) + " y0 " +
+                     std::to_string(window_region_.y0) + " width " +
+                     std::to_string(window_region_.width) + " height " +
+                     std::to_string(window_region_.height));
+}
+
+void
+Reader::check_window(uint32_t first, uint32_t count, const unsplit::Region& R,
+                     const RegionArg& region) const
+{
+    if (window_exact_) {
+        // only the window's own bytes were decoded: the read stays inside its
+        // frames and its region (sums in 64 bits; both regions are valid)
+        const RegionArg& w = window_region_;
+        if (first < window_first_ ||
+            uint64_t(first) + count > uint64_t(window_first_) + window_count_)
+            refuse_read("the read needs frames [" + std::to_string(first) + ", " +
+                        std::to_string(uint64_t(first) + count) + ")");
+        if (region.x0 < w.x0 || region.y0 < w.y0 ||
+            uint64_t(region.x0) + region.width > uint64_t(w.x0) + w.width ||
+            uint64_t(region.y0) + region.height > uint64_t(w.y0) + w.height)
+            refuse_read("the read needs region x0 " + std::to_string(region.x0) + " y0 " +
+                        std::to_string(region.y0) + " width " + std::to_string(region.width) +
+                        " height " + std::to_string(region.height));
+        return;
+    }
     std::vector<uint8_t> mark(g_.n_chunks, 0);
     for (uint32_t f = first; f < first + count; ++f)
         if (!unsplit::region_mark_chunks(g_, R, h_tab_grp_[f], mark.data()))
             throw Error(9, "the frame tables leave the layer");
     for (uint32_t c = 0; c < g_.n_chunks; ++c)
         if (mark[c] && !window_[c])
-            throw Error(1, "the read needs chunk " + std::to_string(c) +
-                             ", outside the loaded window: frames [" +
-                             std::to_string(window_first_) + ", " +
-                             std::to_string(uint64_t(window_first_) + window_count_) +
-                             "), region x0 " + std::to_string(window_region_.x0) + " y0 " +
-                             std::to_string(window_region_.y0) + " width " +
-                             std::to_string(window_region_.width) + " height " +
-                             std::to_string(window_region_.height));
+            refuse_read("the read needs chunk " + std::to_string(c));
+}
+
+std::vector<ChunkRange>
+Reader::region_chunk_ranges(uint32_t first, uint32_t count, const RegionArg* region) const
+{
+    return aqz::region_chunk_ranges(*ad_, first, count, region);
+}
+
+void
+Reader::load_stats(uint64_t* decoded, uint64_t* copied)
+{
+    if (loaded_ == Loaded::None)
+        throw Error(1, "no layer loaded");
+    hip_check(hipEventSynchronize(load_ev_), "hipEventSynchronize");
+    uint64_t sum = stat_decoded_;
+    if (ranged_) {
+        const dec::ByteRange* spans =
+          reinterpret_cast<const dec::ByteRange*>(h_ranges_.p) + g_.n_chunks;
+        sum = 0;
+        for (uint32_t q = 0; q < g_.n_chunks; ++q)
+            sum += spans[q].hi - spans[q].lo;
+    }
+    if (decoded)
+        *decoded = sum;
+    if (copied)
+        *copied = stat_copied_;
 }
 
 std::vector<uint32_t>
@@ -484,7 +589,7 @@ Reader::read_region(uint32_t first, uint32_t count, const RegionArg* region, voi
     if (dst_frame_stride < unsplit::region_frame_extent(g_, q.r))
         throw Error(1, "dst_frame_stride below the region's frame extent");
     if (windowed_)
-        check_window(first, count, q.r);
+        check_window(first, count, q.r, *region);
     q.p.g = g_;
     q.p.src = src_;
     q.p.chunk_src = d_chunk_src_;

@@ -56,6 +56,15 @@ class Reader
                             const uint64_t* offsets, const uint32_t* chunk_of_frame,
                             uint32_t n_frames, int32_t codec, uint32_t first, uint32_t count,
                             const RegionArg* region, hipStream_t stream);
+    // load_frames_region, decoding each chunk of the window over the window's
+    // byte hull only (region_chunk_ranges); chunks outside the window are
+    // neither decoded nor zero-filled, and reads are held to the exact window.
+    // The first call allocates 32 bytes per chunk (device and pinned): the
+    // ranges given to the decoder and the spans it reports.
+    void load_frames_window(const void* frames, size_t frames_bytes, int mem,
+                            const uint64_t* offsets, const uint32_t* chunk_of_frame,
+                            uint32_t n_frames, int32_t codec, uint32_t first, uint32_t count,
+                            const RegionArg* region, hipStream_t stream);
     void load_chunks(const void* chunks, uint64_t pitch, const uint32_t* has_data, uint32_t tag,
                      hipStream_t stream);
     void read_frames(uint32_t first, uint32_t count, void* dst, uint64_t dst_stride,
@@ -66,19 +75,31 @@ class Reader
                      uint64_t dst_row_stride, uint64_t dst_frame_stride, hipStream_t stream);
     std::vector<uint32_t> region_chunks(uint32_t first, uint32_t count,
                                         const RegionArg* region) const;
+    std::vector<ChunkRange> region_chunk_ranges(uint32_t first, uint32_t count,
+                                                const RegionArg* region) const;
     // waits for the last load; status[c] of chunk c, *n_bad = error statuses
     void status(uint32_t* status, size_t cap, uint32_t* n_bad);
+    // waits for the last load.  decoded: chunk bytes its decoder wrote (decoded,
+    // copied out of memcpyed frames or zero-filled; the sum of the spans of a
+    // window load; 0 without a decoder); copied: frame bytes it copied into
+    // the staging buffer.
+    void load_stats(uint64_t* decoded, uint64_t* copied);
 
   private:
     struct Sizes;
     static Sizes sizes(const ReaderDesc& d, const ArrayDimensions& ad);
     void begin_load(hipStream_t stream);
-    // window: per chunk, 1 = inside the loaded window; nullptr = the whole layer
+    // window: per chunk, 1 = inside the loaded window; nullptr = the whole layer.
+    // hull (with a window): the decoder runs over these byte ranges of the
+    // window's chunks, and over nothing of the others.
     void load(const void* frames, size_t frames_bytes, int mem, const uint64_t* offsets,
               const uint32_t* chunk_of_frame, uint32_t n_frames, int32_t codec,
-              const uint8_t* window, hipStream_t stream);
-    // a read of these frames of this region stays inside the loaded window
-    void check_window(uint32_t first, uint32_t count, const unsplit::Region& R) const;
+              const uint8_t* window, const std::vector<ChunkRange>* hull, hipStream_t stream);
+    // a read of these frames of this region stays inside the loaded window;
+    // `region` in acquisition orientation, as the caller gave it
+    void check_window(uint32_t first, uint32_t count, const unsplit::Region& R,
+                      const RegionArg& region) const;
+    [[noreturn]] void refuse_read(const std::string& what) const;
 
     int32_t device_;
     uint32_t codecs_;
@@ -120,6 +141,16 @@ class Reader
     // the window of the last load_frames_region (host memory only): the chunks
     // it loaded, and its description for the error text
     bool windowed_ = false;
+    // the window came from load_frames_window: only its hull was decoded, so a
+    // read has to stay inside its frames and its region, not just its chunks
+    bool window_exact_ = false;
+    // load_frames_window's words, allocated by its first call: device
+    // [ranges n][spans n], and their pinned mirror
+    DevBuf d_ranges_;
+    PinnedBuf h_ranges_;
+    bool ranged_ = false;       // the last load ran the decoder over ranges
+    uint64_t stat_decoded_ = 0; // of the last load (not ranged_)
+    uint64_t stat_copied_ = 0;
     std::vector<uint8_t> window_;
     uint32_t window_first_ = 0, window_count_ = 0;
     RegionArg window_region_{};

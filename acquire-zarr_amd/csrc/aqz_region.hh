@@ -27,4 +27,18 @@ unsplit::Geom unsplit_geom(const ArrayDimensions& ad);
 std::vector<uint32_t> region_chunks(const ArrayDimensions& ad, uint32_t first, uint32_t count,
                                     const RegionArg* region);
 
+// A chunk of region_chunks with the byte hull of the window inside it: the
+// smallest interval [lo, hi) of chunk bytes that holds every byte a crop of
+// `region` from frames [first, first + count) reads (unsplit::region_hull_frame,
+// the crop kernel's own map; tab_off need not rise with the frame).
+struct ChunkRange
+{
+    uint32_t chunk;
+    uint64_t lo, hi;
+};
+// The chunks of region_chunks, in its order and with its errors, each with
+// its hull; lo < hi <= bytes_per_chunk for every one.
+std::vector<ChunkRange> region_chunk_ranges(const ArrayDimensions& ad, uint32_t first,
+                                            uint32_t count, const RegionArg* region);
+
 } // namespace aqz

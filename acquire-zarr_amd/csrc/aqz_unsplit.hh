@@ -424,6 +424,39 @@ region_mark_chunks(const Geom& g, const Region& R, uint32_t grp, uint8_t* mark)
     return true;
 }
 
+// Host: the byte hull of the region inside every chunk a read of one frame
+// touches -- lo[c] falls to the first and hi[c] rises to one past the last
+// chunk byte of the rectangles region_item hands to the mover (start lo at
+// ~0 and hi at 0; a chunk the frame does not touch keeps both).  The walk is
+// region_item's own, so a decoder that produced only [lo[c], hi[c]) of chunk
+// c has produced every byte the crop reads.  False when the map refuses a
+// rectangle (geometry and table disagree).
+inline bool
+region_hull_frame(const Geom& g, const Region& R, uint32_t grp, uint64_t internal, uint64_t* lo,
+                  uint64_t* hi)
+{
+    const uint64_t slab_rows = region_slab_rows(g, R);
+    for (uint64_t j = 0; j < slab_rows; ++j) {
+        uint32_t ty, slab;
+        region_slab_row(g, R, j, ty, slab);
+        for (uint32_t tx = R.tx0; tx < R.tx0 + R.ntx; ++tx) {
+            Rect r;
+            const uint32_t st = region_rect(g, R, grp, internal, ty, tx, slab, r);
+            if (st == kBad)
+                return false;
+            if (st != kMove)
+                continue;
+            const uint64_t a = r.src;
+            const uint64_t b = r.src + (uint64_t(r.rows) - 1) * r.src_pitch + uint64_t(r.cols) * g.bpp;
+            if (a < lo[r.chunk])
+                lo[r.chunk] = a;
+            if (b > hi[r.chunk])
+                hi[r.chunk] = b;
+        }
+    }
+    return true;
+}
+
 // copy_unit for a crop: the clip edges x0 and x0 + w and the crop's row pitch
 // join the word; the frame's own row length does not (a rectangle is cut
 // either at a tile edge or at a region edge).  `align` also holds the

@@ -261,7 +261,148 @@ zstd_finish(DecodeParams p)
         p.bad[q] = 1;
 }
 
+// ---- ranged decode ----------------------------------------------------------
+// zstd_decode and zstd_finish over the blocks of a blosc1-zstd frame that meet
+// a byte range (aqz_decode.hh, RangedParams; no compare mode).  Kernels of
+// their own, so that the code of a full run is what it was.  The blocks of a
+// frame are independent zstd frames: blocks [jlo, jhi) are dealt to the
+// passes from jlo on.  A plain zstd frame is decoded whole, as in a full run
+// (its matches reach across blocks), and reports the whole chunk.  Empty and
+// bad ranges got their status from blosc_decode_ranged and are left alone.
+__global__ void __launch_bounds__(64)
+zstd_decode_ranged(RangedParams rp)
+{
+    __shared__ zdec::Tables s_t;
+    const DecodeParams& p = rp.p;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    const bool lead = blockIdx.y == 0 && lane == 0;
+    const dec::ByteRange want = rp.ranges[q];
+    if (dec::range_status(want, p.chunk_bytes) != dec::kOk)
+        return;
+    FrameRef r;
+    if (!frame_ref(p, q, r) || r.len == 0 || dec::frame_family(r.f, r.len) != dec::kFamilyZstd)
+        return;
+    const uint32_t len = uint32_t(r.len);
+    uint8_t* scr = p.scratch + uint64_t(q) * p.scratch_pitch;
+    uint8_t* lit = p.zlit + (uint64_t(q) * p.zpasses + blockIdx.y) * p.zlit_pitch;
+    const uint32_t magic = dec::rd32(r.f);
+    if (magic == dec::kZstdMagic || (magic & 0xfffffff0u) == dec::kSkippableMagic) {
+        if (lead)
+            put_span(rp, q, 0, p.chunk_bytes);
+        if (blockIdx.y != 0 || (p.zfr && p.zfr[2 * q] != 0)) // the parallel path's frame
+            return;
+        WaveZIo io{ r.f, r.out, lit, lane };
+        const uint32_t e = zdec::zstd_decode_frame(io, r.f, len, uint32_t(p.chunk_bytes), s_t);
+        if (e != dec::kOk && lane == 0)
+            atomicMax(&p.status[q], e);
+        return;
+    }
+    dec::FrameInfo h;
+    const uint32_t st = dec::parse_header(r.f, r.len, p.chunk_bytes, h, dec::kCodecZstd);
+    if (st != dec::kOk) {
+        if (lead)
+            atomicMax(&p.status[q], st);
+        return;
+    }
+    if (h.memcpyed) {
+        bool diff = false;
+        if (lead)
+            put_span(rp, q, want.lo, want.hi);
+        const uint64_t step = uint64_t(gridDim.y) * kDecodeLdsBytes;
+        for (uint64_t b = want.lo + uint64_t(blockIdx.y) * kDecodeLdsBytes; b < want.hi;
+             b += step) {
+            const uint64_t left = want.hi - b;
+            const uint32_t n = left < kDecodeLdsBytes ? uint32_t(left) : kDecodeLdsBytes;
+            copy_bytes<false>(r.out + b, r.f + 16 + b, n, lane, 64, diff);
+        }
+        return;
+    }
+    // want.hi <= chunk_bytes == h.nbytes and want.lo < want.hi: at least one block
+    const dec::BlockRange br = dec::blocks_of_range(h, want.lo, want.hi);
+    if (lead)
+        put_span(rp, q, br.lo, br.hi);
+    uint8_t* base = staged<false>(false, h.mode) ? scr : r.out;
+    uint32_t err = dec::kOk;
+    for (uint32_t j = br.jlo + blockIdx.y; j < br.jhi && err == dec::kOk; j += gridDim.y) {
+        const dec::BlockInfo bi = dec::block_info(h, j);
+        uint32_t pos = 0;
+        err = dec::block_start(r.f, h, j, pos);
+        for (uint32_t s = 0; s < bi.ns && err == dec::kOk; ++s) {
+            uint32_t src = 0, csz = 0;
+            err = dec::next_stream(r.f, h, pos, src, csz);
+            if (err != dec::kOk)
+                break;
+            src = uni(src);
+            csz = uni(csz);
+            WaveZIo io{ r.f + src, base + uint64_t(j) * h.blocksize + uint64_t(s) * bi.slen, lit,
+                        lane };
+            if (csz == bi.slen) { // stored raw
+                if (bi.slen)
+                    io.copy_src(0, 0, bi.slen);
+            } else {
+                err = zdec::zstd_decode_frame(io, r.f + src, csz, bi.slen, s_t);
+            }
+        }
+    }
+    if (err != dec::kOk && lane == 0)
+        atomicMax(&p.status[q], err);
+}
+
+__global__ void __launch_bounds__(kFinishThreads)
+zstd_finish_ranged(RangedParams rp)
+{
+    const DecodeParams& p = rp.p;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    const dec::ByteRange want = rp.ranges[q];
+    if (dec::range_status(want, p.chunk_bytes) != dec::kOk)
+        return;
+    FrameRef r;
+    if (!frame_ref(p, q, r) || r.len == 0 || dec::frame_family(r.f, r.len) != dec::kFamilyZstd)
+        return;
+    if (p.status[q] != dec::kOk) // written by zstd_decode_ranged, complete before this kernel
+        return;
+    if (dec::rd32(r.f) == dec::kZstdMagic) // decoded in place
+        return;
+    dec::FrameInfo h;
+    if (dec::parse_header(r.f, r.len, p.chunk_bytes, h, dec::kCodecZstd) != dec::kOk ||
+        h.memcpyed || !staged<false>(false, h.mode))
+        return;
+    const dec::BlockRange br = dec::blocks_of_range(h, want.lo, want.hi);
+    const uint8_t* scr = p.scratch + uint64_t(q) * p.scratch_pitch;
+    bool diff = false;
+    for (uint32_t j = br.jlo + blockIdx.y; j < br.jhi; j += gridDim.y) {
+        const dec::BlockInfo bi = dec::block_info(h, j);
+        unshuffle_block<false>(scr + uint64_t(j) * h.blocksize, r.out + uint64_t(j) * h.blocksize,
+                               bi.bsize, h.typesize, h.mode, tid, kFinishThreads, diff);
+    }
+}
+
 } // namespace
+
+hipError_t
+launch_zstd_decode_ranged(const RangedParams& rp, uint64_t max_range_bytes, hipStream_t stream)
+{
+    const DecodeParams& p = rp.p;
+    if (p.n_chunks == 0)
+        return hipSuccess;
+    if (!rp.ranges || p.bad || !p.scratch || !p.zlit || p.zpasses == 0 ||
+        p.zpasses > kZstdMaxPasses || p.scratch_pitch < p.chunk_bytes ||
+        p.zlit_pitch < zstd_decode_lit_pitch(p.chunk_bytes))
+        return hipErrorInvalidValue;
+    // a literal slot per (chunk, pass): no more passes than a full run takes
+    uint32_t passes = zstd_decode_passes(p.chunk_bytes);
+    if (passes > p.zpasses)
+        passes = p.zpasses;
+    const dim3 grid(p.n_chunks, ranged_passes(p.chunk_bytes, max_range_bytes, passes));
+    hipLaunchKernelGGL(zstd_decode_ranged, grid, dim3(64), 0, stream, rp);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(zstd_finish_ranged, grid, dim3(kFinishThreads), 0, stream, rp);
+    return hipGetLastError();
+}
 
 uint32_t
 zstd_decode_passes(uint64_t max_chunk_bytes)

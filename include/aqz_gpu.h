@@ -922,6 +922,77 @@ aqz_status aqz_reader_read_region(aqz_reader* r, uint32_t first, uint32_t count,
                                   const aqz_region* region, void* dst, uint64_t dst_row_stride,
                                   uint64_t dst_frame_stride, void* stream);
 
+/* ---- window loads: decode only the blosc blocks a region read needs ----------
+ * Every block of a blosc1 frame is compressed and shuffled on its own, and a
+ * frame's tile inside a chunk is one contiguous run of bytes, so a crop of a few
+ * frames needs a short byte interval of each of its chunks, and of the frame only
+ * the blocks that meet it.  Chunk bytes [lo, hi). */
+typedef struct
+{
+    uint64_t lo, hi;
+} aqz_byte_range;
+/* aqz_dims_region_chunks with, for chunks[i], ranges[i]: the smallest interval of
+ * chunk bytes that holds every byte a crop of `region` from frames [first, first +
+ * count) reads (0 <= lo < hi <= bytes_per_chunk), through transpose_frame_id and an
+ * XY-swapped storage order.  Host only.  *n = the count needed, always; chunks or
+ * ranges NULL: that array is not filled (both NULL: count only); cap < *n with an
+ * array given: AQZ_STATUS_OVERFLOW.  The arguments are checked, and refused with the
+ * texts, as aqz_dims_region_chunks does. */
+aqz_status aqz_dims_region_chunk_ranges(const aqz_dims* d, uint32_t first, uint32_t count,
+                                        const aqz_region* region, uint32_t* chunks,
+                                        aqz_byte_range* ranges, size_t cap, uint32_t* n);
+/* The same for a reader's own dims. */
+aqz_status aqz_reader_region_chunk_ranges(const aqz_reader* r, uint32_t first, uint32_t count,
+                                          const aqz_region* region, uint32_t* chunks,
+                                          aqz_byte_range* ranges, size_t cap, uint32_t* n);
+/* aqz_decompressor_run over chunk bytes ranges[i] of frame i only (ranges: device,
+ * n_chunks entries; spans: device, n_chunks entries, may be NULL).  Per frame:
+ *  - a blosc1 frame (LZ4 or zstd codec; any block size, split or not, any shuffle):
+ *    only blocks [lo / blocksize, ceil(hi / blocksize)) are looked up in the block
+ *    table, decoded and un-shuffled; spans[i] is the block-aligned interval
+ *    [jlo * blocksize, min(jhi * blocksize, chunk_bytes)).  Of the frame, only the
+ *    header, those blocks' table entries and their records are read: a defect
+ *    elsewhere is not looked at and not reported; one inside gets the status a full
+ *    decode gives it.
+ *  - a memcpyed or zero-length frame: exactly [lo, hi) is copied or zero-filled;
+ *    spans[i] = ranges[i].
+ *  - a plain zstd frame is decoded whole (its matches reach across blocks), by the
+ *    block-parallel kernels where the decoder has them; spans[i] = [0, chunk_bytes).
+ *  - lo == hi: the frame is not decoded, status[i] = AQZ_DECODE_NOT_LOADED, empty
+ *    span.  lo > hi or hi > chunk_bytes: status[i] = AQZ_DECODE_BAD_HEADER, empty
+ *    span.  An empty span is {0, 0}; so is the span of a frame whose header is
+ *    refused.
+ * No byte of chunk i outside spans[i] is written. */
+aqz_status aqz_decompressor_run_ranges(aqz_decompressor* d, const void* frames,
+                                       size_t frames_bytes, const uint64_t* offsets,
+                                       uint32_t n_chunks, void* dst, uint64_t pitch,
+                                       uint64_t chunk_bytes, const aqz_byte_range* ranges,
+                                       aqz_byte_range* spans, uint32_t* status, void* stream);
+/* aqz_reader_load_frames_region, decoding only the window's bytes: the frames of
+ * the window's chunks are copied and packed the same way (whole frames: the block
+ * table is needed), each is decoded over its aqz_reader_region_chunk_ranges hull
+ * only, and the chunks outside the window get an empty range -- they are neither
+ * decoded nor zero-filled (AQZ_DECODE_NOT_LOADED).  The reader remembers the exact
+ * window until the next load: a read_region or read_frames whose frames are not
+ * inside [first, first + count) or whose region is not inside `region` is
+ * AQZ_STATUS_INVALID_ARGUMENT, the text names the window, and nothing is enqueued
+ * (a byte that was not decoded is never handed out).  Stored chunks
+ * (AQZ_CODEC_NONE) are loaded as by the region load.  The first call on a reader
+ * with codecs allocates 32 bytes per chunk of device memory (and as much pinned):
+ * the ranges and the spans; aqz_reader_device_bytes does not count them. */
+aqz_status aqz_reader_load_frames_window(aqz_reader* r, const void* frames, size_t frames_bytes,
+                                         int32_t mem, const uint64_t* offsets,
+                                         const uint32_t* chunk_of_frame, uint32_t n_frames,
+                                         int32_t codec, uint32_t first, uint32_t count,
+                                         const aqz_region* region, void* stream);
+/* Waits for the last load.  *decoded_bytes: the chunk bytes its decoder wrote --
+ * the sum of the spans of a window load; chunks_per_layer * bytes_per_chunk after
+ * aqz_reader_load_frames or aqz_reader_load_frames_region with a codec (a region
+ * load zero-fills the chunks outside its window); 0 for stored chunks and
+ * aqz_reader_load_chunks.  *copied_bytes: the frame bytes it copied into the
+ * staging buffer.  Either may be NULL. */
+aqz_status aqz_reader_load_stats(aqz_reader* r, uint64_t* decoded_bytes, uint64_t* copied_bytes);
+
 #ifdef __cplusplus
 }
 #endif

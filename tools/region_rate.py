@@ -16,7 +16,16 @@ warm-up call:
        --codec zstd: plain zstd, decoded with AQZ_DECODE_ZSTD_PARALLEL.  Reported
        as a ratio of times next to the ratio of chunks decoded.
 
+  --window adds, in the same process, beside every load_frames_region + read_region
+  row: load_frames_window + read_region of the same crop (decoding only the blosc blocks
+  the crop's byte hull meets), and a window equal to the whole layer beside the region
+  load of the whole layer.  Each row is timed twice; the spread of the region row's two
+  runs is the margin.  Every line carries load_stats (decoded bytes, copied bytes).
+  --codec blosc-zstd (blosc-zstd with the byte shuffle) is for this mode.
+
   python3 tools/region_rate.py --codec lz4 [--reps 20] [--out profiles/r10_region_rate.jsonl]
+  python3 tools/region_rate.py --window --codec lz4|blosc-zstd|zstd \
+      --out profiles/r11_window_rate.jsonl
 """
 import argparse
 import json
@@ -59,7 +68,9 @@ def timed(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--codec", choices=("lz4", "zstd"), default="lz4")
+    ap.add_argument("--codec", choices=("lz4", "blosc-zstd", "zstd"), default="lz4")
+    ap.add_argument("--window", action="store_true",
+                    help="time load_frames_window beside every load_frames_region row")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r10_region_rate.jsonl"))
     args = ap.parse_args()
@@ -80,6 +91,8 @@ def main():
 
     if args.codec == "lz4":
         code, codecs, shuffle = aqz.CODEC_BLOSC_LZ4, aqz.DECODE_CODEC_LZ4, 1
+    elif args.codec == "blosc-zstd":
+        code, codecs, shuffle = aqz.CODEC_BLOSC_ZSTD, aqz.DECODE_CODEC_ZSTD, 1
     else:
         code, shuffle = aqz.CODEC_ZSTD, 0
         codecs = aqz.DECODE_CODEC_ZSTD | aqz.DECODE_ZSTD_PARALLEL
@@ -107,7 +120,7 @@ def main():
                 "read_region_whole_exact": exact})
 
     # (ii) a 512 x 512 crop of one frame against the full load + read
-    st.compress_layer(0, 0, codec=code, clevel=3 if args.codec == "zstd" else 5, shuffle=shuffle)
+    st.compress_layer(0, 0, codec=code, clevel=5 if args.codec == "lz4" else 3, shuffle=shuffle)
     off = st.compressed_offsets(0, 0)
     total = int(off[-1])
     cfr = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -122,7 +135,8 @@ def main():
     full_ms = timed(full, args.reps)
     _, bad = rd.status()
     row.update({"compressed_bytes": total, "full_ms": round(full_ms, 3),
-                "full_exact": bool(torch.equal(out, frames)) and bad == 0})
+                "full_exact": bool(torch.equal(out, frames)) and bad == 0,
+                "full_load_stats": list(rd.load_stats())})
     crop = torch.empty(CROP * CROP * 2, dtype=torch.uint8, device=dev)
     for key, (x0, y0) in (("aligned", (256, 256)), ("unaligned", (129, 131))):
         region = (x0, y0, CROP, CROP)
@@ -138,11 +152,59 @@ def main():
         ms = timed(crop_read, args.reps)
         _, bad = rd.status()
         want = images[FRAME, y0:y0 + CROP, x0:x0 + CROP].contiguous().view(torch.uint8).flatten()
+        if args.window:
+            # the same crop through the window load, the region row timed again beside it
+            def window_read():
+                rd.load_frames_window(cfr, off, FRAME, 1, region, None, code,
+                                      frames_bytes=total, stream_ptr=stream)
+                rd.read_region_ptr(FRAME, 1, region, crop.data_ptr(), CROP * 2,
+                                   CROP * CROP * 2, stream)
+
+            region_stats = list(rd.load_stats())
+            ms2 = timed(crop_read, args.reps)
+            crop.zero_()
+            w1 = timed(window_read, args.reps)
+            _, wbad = rd.status()
+            w_exact = bool(torch.equal(crop, want)) and wbad == 0
+            w_stats = list(rd.load_stats())
+            w2 = timed(window_read, args.reps)
+            row.update({key + "_region_ms": [round(ms, 4), round(ms2, 4)],
+                        key + "_window_ms": [round(w1, 4), round(w2, 4)],
+                        key + "_region_spread": round(abs(ms - ms2) / min(ms, ms2), 4),
+                        key + "_window_over_region": round(min(w1, w2) / min(ms, ms2), 4),
+                        key + "_region_load_stats": region_stats,
+                        key + "_window_load_stats": w_stats,
+                        key + "_window_exact": w_exact})
+            crop.zero_()
+            crop_read()
+            torch.cuda.synchronize()
         row.update({key + "_origin": [x0, y0], key + "_chunks": n_need,
                     key + "_ms": round(ms, 4),
                     key + "_time_ratio": round(ms / full_ms, 4),
                     key + "_chunk_ratio": round(n_need / N_CHUNKS, 4),
                     key + "_exact": bool(torch.equal(crop, want)) and bad == 0})
+    if args.window:
+        # a window equal to the whole layer beside the region load of the whole layer
+        def whole_read(window):
+            load = rd.load_frames_window if window else rd.load_frames_region
+            load(cfr, off, 0, PLANES, whole, None, code, frames_bytes=total, stream_ptr=stream)
+            rd.read_region_ptr(0, PLANES, whole, out.data_ptr(), SIDE * 2, frame_bytes, stream)
+
+        g1 = timed(lambda: whole_read(False), args.reps)
+        g_stats = list(rd.load_stats())
+        g2 = timed(lambda: whole_read(False), args.reps)
+        out.zero_()
+        w1 = timed(lambda: whole_read(True), args.reps)
+        _, wbad = rd.status()
+        w_exact = bool(torch.equal(out, frames)) and wbad == 0
+        w_stats = list(rd.load_stats())
+        w2 = timed(lambda: whole_read(True), args.reps)
+        row.update({"whole_region_ms": [round(g1, 3), round(g2, 3)],
+                    "whole_window_ms": [round(w1, 3), round(w2, 3)],
+                    "whole_region_spread": round(abs(g1 - g2) / min(g1, g2), 4),
+                    "whole_window_over_region": round(min(w1, w2) / min(g1, g2), 4),
+                    "whole_region_load_stats": g_stats, "whole_window_load_stats": w_stats,
+                    "whole_window_exact": w_exact})
     rd.close()
     st.close()
     print(json.dumps(row), flush=True)
