@@ -288,6 +288,8 @@ def lib():
         "aqz_stage_set_stream": ([vp, vp], i32),
         "aqz_stage_set_tuning": ([vp, u32, u32], i32),
         "aqz_stage_append": ([vp, vp, u64, i32], i32),
+        "aqz_stage_append_strided": ([vp, vp, u64, i32, u64, u64], i32),
+        "aqz_stage_source_report": ([vp, C.POINTER(u64), C.POINTER(u64)], i32),
         "aqz_stage_synchronize": ([vp], i32),
         "aqz_stage_frames_written": ([vp, u32], u64),
         "aqz_stage_copy_layer": ([vp, u32, u64, vp, sz, vp, sz, i32], i32),
@@ -637,6 +639,29 @@ def _ptr(buf):
     raise TypeError(type(buf))
 
 
+def _pitched(buf):
+    """(pointer, mem kind, row stride, frame stride) in bytes of a 3-D numpy
+    array or torch tensor that is not contiguous but whose rows are: its last
+    stride is one element and its other strides are positive.  None for
+    anything else."""
+    if isinstance(buf, np.ndarray):
+        if buf.ndim != 3 or buf.flags.c_contiguous or 0 in buf.shape:
+            return None
+        item, strides = buf.itemsize, buf.strides
+        p, mem = buf.ctypes.data, MEM_HOST
+    elif hasattr(buf, "data_ptr"):
+        if buf.ndim != 3 or buf.is_contiguous() or 0 in buf.shape:
+            return None
+        item = buf.element_size()
+        strides = tuple(st * item for st in buf.stride())
+        p, mem = buf.data_ptr(), (MEM_DEVICE if buf.is_cuda else MEM_HOST)
+    else:
+        return None
+    if strides[2] != item or strides[0] <= 0 or strides[1] <= 0:
+        return None
+    return p, mem, strides[1], strides[0]
+
+
 class Downsampler:
     """zarr::Downsampler on the GPU: add_frame / take_frame."""
 
@@ -775,8 +800,16 @@ class Stage:
         or a torch tensor.  A CUDA tensor is read on the stage's own stream:
         that stream first waits for the work torch has queued on the
         tensor's current stream (no host sync), and the tensor is kept
-        alive until the stage reports its frames consumed."""
-        p, mem = _ptr(frames)
+        alive until the stage reports its frames consumed.  A 3-D array or
+        tensor that is a view with contiguous rows (a last stride of one
+        element, the other strides positive; e.g. frames[:, y0:y1, x0:x1])
+        is appended from where it lies, by its strides
+        (aqz_stage_append_strided); any other non-contiguous one raises."""
+        pitched = _pitched(frames)
+        if pitched:
+            p, mem, row_stride, frame_stride = pitched
+        else:
+            p, mem = _ptr(frames)
         if n_frames is None:
             n_frames = frames.shape[0] if frames.ndim == 3 else 1
         cuda = mem == MEM_DEVICE and hasattr(frames, "data_ptr")
@@ -784,7 +817,11 @@ class Stage:
             import torch
             s = torch.cuda.current_stream(frames.device).cuda_stream
             _check(lib().aqz_stage_wait_stream(self.h, s), "wait_stream")
-        _check(lib().aqz_stage_append(self.h, p, n_frames, mem), "append")
+        if pitched:
+            _check(lib().aqz_stage_append_strided(self.h, p, n_frames, mem, row_stride,
+                                                  frame_stride), "append_strided")
+        else:
+            _check(lib().aqz_stage_append(self.h, p, n_frames, mem), "append")
         self._appended += n_frames
         if cuda:
             self._held.append((self._appended, frames))
@@ -795,6 +832,27 @@ class Stage:
         memory (see frames_consumed)."""
         _check(lib().aqz_stage_append(self.h, ptr, n_frames, mem), "append")
         self._appended += n_frames
+
+    def append_strided(self, ptr_or_buffer, n_frames, row_stride, frame_stride,
+                       mem=MEM_DEVICE):
+        """aqz_stage_append_strided: n_frames pitched frames whose pixel
+        (0, 0) is at a raw pointer (memory kind `mem`) or at the start of a
+        HostBuffer (pinned); row y of frame k starts k * frame_stride +
+        y * row_stride bytes on.  The caller orders and keeps the memory
+        (see frames_consumed)."""
+        if isinstance(ptr_or_buffer, HostBuffer):
+            ptr_or_buffer, mem = ptr_or_buffer.ptr, MEM_HOST_PINNED
+        _check(lib().aqz_stage_append_strided(self.h, ptr_or_buffer, n_frames, mem,
+                                              row_stride, frame_stride), "append_strided")
+        self._appended += n_frames
+
+    def source_report(self):
+        """(direct, packed): device frames of pitched appends read in place
+        by the fused kernels / packed by the copy kernel first
+        (aqz_stage_source_report); contiguous and host frames in neither."""
+        d, k = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().aqz_stage_source_report(self.h, C.byref(d), C.byref(k)), "source_report")
+        return d.value, k.value
 
     def wait_stream(self, stream_ptr):
         _check(lib().aqz_stage_wait_stream(self.h, stream_ptr), "wait_stream")

@@ -817,6 +817,17 @@ aqz_stage_append(aqz_stage* st, const void* frames, uint64_t n_frames,
 }
 
 aqz_status
+aqz_stage_append_strided(aqz_stage* st, const void* frames, uint64_t n_frames, int32_t mem,
+                         uint64_t row_stride, uint64_t frame_stride)
+{
+    return guard_sticky(st, [&] {
+        if (mem != AQZ_MEM_HOST && mem != AQZ_MEM_DEVICE && mem != AQZ_MEM_HOST_PINNED)
+            throw aqz::Error(AQZ_STATUS_INVALID_ARGUMENT, "unknown memory kind");
+        st->st->append_strided(frames, n_frames, mem, row_stride, frame_stride);
+    });
+}
+
+aqz_status
 aqz_stage_synchronize(aqz_stage* st)
 {
     return guard_sticky(st, [&] { st->st->synchronize(); });
@@ -991,6 +1002,15 @@ const char*
 aqz_stage_dominant_kernel(const aqz_stage* st)
 {
     return st ? st->st->dominant_kernel() : "";
+}
+
+aqz_status
+aqz_stage_source_report(const aqz_stage* st, uint64_t* direct_frames, uint64_t* packed_frames)
+{
+    if (!st || !st->st)
+        return AQZ_STATUS_INVALID_ARGUMENT;
+    st->st->source_report(direct_frames, packed_frames);
+    return AQZ_STATUS_SUCCESS;
 }
 
 uint32_t

@@ -95,7 +95,20 @@ CopyPool::piece(size_t i)
     if (lo >= n_)
         return;
     const size_t len = lo + per > n_ ? n_ - lo : per;
-    std::memcpy(dst_ + lo, src_ + lo, len);
+    if (rows_ == 0) {
+        std::memcpy(dst_ + lo, src_ + lo, len);
+        return;
+    }
+    // rows [lo, lo + len) of the packed frames
+    size_t k = lo / rows_, y = lo - k * rows_;
+    for (size_t r = lo; r < lo + len; ++r) {
+        std::memcpy(dst_ + r * row_bytes_, src_ + k * frame_stride_ + y * row_stride_,
+                    row_bytes_);
+        if (++y == rows_) {
+            y = 0;
+            ++k;
+        }
+    }
 }
 
 void
@@ -132,9 +145,43 @@ CopyPool::copy(void* dst, const void* src, size_t n)
         dst_ = static_cast<uint8_t*>(dst);
         src_ = static_cast<const uint8_t*>(src);
         n_ = n;
+        rows_ = 0;
         pieces_ = threads_.size() + 1;
         pending_ = unsigned(threads_.size());
         ++gen_;
+    }
+    go_.notify_all();
+    piece(0);
+    std::unique_lock<std::mutex> lk(mu_);
+    done_.wait(lk, [&] { return pending_ == 0; });
+}
+
+void
+CopyPool::copy_rows(void* dst, const void* src, size_t n_frames, size_t rows, size_t row_bytes,
+                    size_t row_stride, size_t frame_stride, size_t min_piece)
+{
+    const size_t n = n_frames * rows;
+    if (n == 0 || row_bytes == 0)
+        return;
+    const bool alone = threads_.empty() || n * row_bytes < 2 * min_piece;
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        dst_ = static_cast<uint8_t*>(dst);
+        src_ = static_cast<const uint8_t*>(src);
+        n_ = n;
+        rows_ = rows;
+        row_bytes_ = row_bytes;
+        row_stride_ = row_stride;
+        frame_stride_ = frame_stride;
+        pieces_ = alone ? 1 : threads_.size() + 1;
+        if (!alone) {
+            pending_ = unsigned(threads_.size());
+            ++gen_;
+        }
+    }
+    if (alone) {
+        piece(0);
+        return;
     }
     go_.notify_all();
     piece(0);

@@ -34,6 +34,13 @@ class CopyPool
 
     // dst[0, n) = src[0, n); returns when every piece is done
     void copy(void* dst, const void* src, size_t n);
+    // Pitched frames packed: row y of frame k, row_bytes long, from src +
+    // k * frame_stride + y * row_stride to dst + (k * rows + y) * row_bytes.
+    // Only the row_bytes of each row are read.  The rows are split over the
+    // workers as copy splits its bytes; min_piece: bytes below which a
+    // piece is not worth a worker (tests lower it).
+    void copy_rows(void* dst, const void* src, size_t n_frames, size_t rows, size_t row_bytes,
+                   size_t row_stride, size_t frame_stride, size_t min_piece = size_t(4) << 20);
     unsigned workers() const { return unsigned(threads_.size()); }
 
   private:
@@ -49,6 +56,8 @@ class CopyPool
     uint8_t* dst_ = nullptr;
     const uint8_t* src_ = nullptr;
     size_t n_ = 0, pieces_ = 0;
+    // copy_rows: n_ counts rows (0 rows_: a plain copy)
+    size_t rows_ = 0, row_bytes_ = 0, row_stride_ = 0, frame_stride_ = 0;
 };
 
 } // namespace aqz

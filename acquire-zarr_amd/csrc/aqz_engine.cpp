@@ -4,6 +4,7 @@
 #include "aqz_engine.hh"
 
 #include <hsa/hsa_ext_amd.h>
+#include "aqz_strided.hh"
 #include "aqz_zstd.hh"
 
 #include <algorithm>
@@ -1229,12 +1230,88 @@ Stage::wait_copies()
 void
 Stage::append(const void* frames, uint64_t n_frames, int mem)
 {
+    append_frames(frames, n_frames, mem, 0, 0);
+}
+
+void
+Stage::append_strided(const void* frames, uint64_t n_frames, int mem, uint64_t row_stride,
+                      uint64_t frame_stride)
+{
+    if (n_frames == 0)
+        return;
+    if (!frames)
+        throw Error(1, "null frames");
+    // the frames as appended: acquisition rows for an XY-swapped storage order
+    const strided::Shape shape{ xy_ ? acq_cols_ : lv_[0].W, xy_ ? acq_rows_ : lv_[0].H, bpp_ };
+    if (const char* why =
+          strided::refusal(shape, reinterpret_cast<uintptr_t>(frames), n_frames, row_stride,
+                           frame_stride, opt_.level0_on_host))
+        throw Error(1, why);
+    if (strided::contiguous(shape, row_stride, frame_stride))
+        append_frames(frames, n_frames, mem, 0, 0);
+    else
+        append_frames(frames, n_frames, mem, row_stride, frame_stride);
+}
+
+// Batch b of a pitched host source into d_stage_[j], packed.  A pinned source
+// is DMA'd from its rows (its frames are consumed when h2d_ gets there); a
+// pageable one, or a pitch the runtime's 2-D copy refuses, goes through
+// copy_rows and the pinned staging buffer first.
+void
+Stage::stage_host_rows(int j, const uint8_t* p, uint32_t b, bool pinned, uint64_t row_stride,
+                       uint64_t frame_stride)
+{
+    const uint64_t rows = xy_ ? acq_rows_ : lv_[0].H;
+    const uint64_t rbytes = uint64_t(xy_ ? acq_cols_ : lv_[0].W) * bpp_;
+    const uint64_t fbytes = rows * rbytes;
+    if (consume_rec_[j]) // kernels of the batch before last read d_stage_[j]
+        hip_check(hipStreamWaitEvent(h2d_, consume_ev_[j], 0), "hipStreamWaitEvent");
+    if (strided::host_route(pinned) == strided::kHostPinned) {
+        // one 2-D copy for the batch when its frames' rows are equally spaced
+        const bool one = frame_stride == rows * row_stride;
+        const uint32_t calls = one ? 1 : b;
+        const uint64_t h = one ? rows * b : rows;
+        hipError_t e = hipSuccess;
+        uint32_t c = 0;
+        for (; c < calls && e == hipSuccess; ++c)
+            e = hipMemcpy2DAsync(d_stage_[j].p + c * fbytes, rbytes, p + c * frame_stride,
+                                 row_stride, rbytes, h, hipMemcpyHostToDevice, h2d_);
+        if (e == hipSuccess) {
+            hip_check(hipEventRecord(h2d_ev_[j], h2d_), "hipEventRecord");
+            note_consumed(h2d_, b);
+            return;
+        }
+        (void)hipGetLastError();
+        if (!(e == hipErrorInvalidPitchValue || e == hipErrorInvalidValue) || c > 1)
+            hip_check(e, "hipMemcpy2DAsync");
+        // the first call refused the pitch: nothing is enqueued, stage the rows
+    }
+    h_stage_[j].alloc(size_t(opt_.max_batch_frames) * fbytes);
+    hip_check(hipEventSynchronize(h2d_ev_[j]), "hipEventSynchronize");
+    if (!pool_)
+        pool_ = std::make_unique<CopyPool>(copy_workers(), numa_cpus_);
+    pool_->copy_rows(h_stage_[j].p, p, b, rows, rbytes, row_stride, frame_stride);
+    memcpy_pieces(d_stage_[j].p, h_stage_[j].p, size_t(b) * fbytes, hipMemcpyHostToDevice,
+                  h2d_);
+    hip_check(hipEventRecord(h2d_ev_[j], h2d_), "hipEventRecord");
+    note_consumed(nullptr, b); // copied into staging before return
+}
+
+// row_stride == 0: contiguous frames (append); else a pitched source whose
+// arguments append_strided has checked.
+void
+Stage::append_frames(const void* frames, uint64_t n_frames, int mem, uint64_t row_stride,
+                     uint64_t frame_stride)
+{
     if (n_frames == 0)
         return;
     if (!frames)
         throw Error(1, "null frames");
     finalized_ = false;
-    const uint64_t fbytes = uint64_t(lv_[0].W) * lv_[0].H * bpp_;
+    const bool pitched = row_stride != 0;
+    const uint64_t fbytes =
+      pitched ? frame_stride : uint64_t(lv_[0].W) * lv_[0].H * bpp_; // source frame to frame
+    const uint64_t packed_fbytes = uint64_t(lv_[0].W) * lv_[0].H * bpp_;
     uint64_t n_ok = n_frames;
     if (max_frames_ > 0) {
         uint64_t room = max_frames_ - std::min(max_frames_, lv_[0].frames_written);
@@ -1255,8 +1332,65 @@ Stage::append(const void* frames, uint64_t n_frames, int mem)
         if (slab_len_) // a batch never straddles two slabs
             b = uint32_t(std::min<uint64_t>(b, slab_len_ - slab_done_));
         const uint8_t* p = src + done * fbytes;
-        if (mem == kMemDevice) {
+        if (mem == kMemDevice && pitched) {
+            // frames the fused kernels load in place, then the ones packed first
+            strided::StageKind kind;
+            kind.xy = xy_;
+            kind.fused_2d = fused_2d_;
+            kind.pitched_3d = !fused_2d_ && fused_3d_ && rh_log2_ == 6 && n_levels() - 1 <= 4 &&
+                              (zmask3d_ & 2u) && g3d_ % 2 == 0;
+            kind.group = g3d_;
+            kind.default_tuning = knobs_ == 0 && nt_mode_ == 7;
+            bool pending = false;
+            for (const auto& pd : pend_)
+                pending |= pd.has;
+            const strided::DevicePlan plan = strided::plan_device_batch(
+              kind, reinterpret_cast<uintptr_t>(p), row_stride, frame_stride, b,
+              lv_[0].frames_written, pending);
+            if (plan.direct) {
+                pitch_row_ = row_stride;
+                pitch_frame_ = frame_stride;
+                try {
+                    run_batch(p, plan.direct);
+                } catch (...) {
+                    pitch_row_ = pitch_frame_ = 0;
+                    throw;
+                }
+                pitch_row_ = pitch_frame_ = 0;
+                direct_frames_ += plan.direct;
+            }
+            if (plan.packed) {
+                const strided::Shape shape{ xy_ ? acq_cols_ : lv_[0].W,
+                                            xy_ ? acq_rows_ : lv_[0].H, bpp_ };
+                pack_buf_.alloc(size_t(B) * packed_fbytes);
+                PackParams pp{};
+                pp.src = p + uint64_t(plan.direct) * frame_stride;
+                pp.dst = pack_buf_.p;
+                pp.row_stride = row_stride;
+                pp.frame_stride = frame_stride;
+                pp.row_bytes = strided::row_bytes(shape);
+                pp.rows = uint32_t(shape.H);
+                pp.n_frames = plan.packed;
+                hip_check(launch_pack_frames(
+                            pp,
+                            strided::pack_unit(shape, reinterpret_cast<uintptr_t>(pp.src),
+                                               row_stride, frame_stride),
+                            stream_),
+                          "pack_frames launch");
+                run_batch(pack_buf_.p, plan.packed);
+                packed_frames_ += plan.packed;
+            }
+        } else if (mem == kMemDevice) {
             run_batch(p, b);
+        } else if (pitched) {
+            const int j = stage_idx_;
+            stage_idx_ ^= 1;
+            alloc_large(d_stage_[j], size_t(B) * packed_fbytes, opt_.codec.vmm);
+            stage_host_rows(j, p, b, mem == kMemHostPinned, row_stride, frame_stride);
+            hip_check(hipStreamWaitEvent(stream_, h2d_ev_[j], 0), "hipStreamWaitEvent");
+            run_batch(d_stage_[j].p, b);
+            hip_check(hipEventRecord(consume_ev_[j], stream_), "hipEventRecord");
+            consume_rec_[j] = true;
         } else {
             // Double buffer: batch i+1's host copy and H2D (on h2d_) overlap
             // batch i's kernels.  A pageable source is first copied into the
@@ -1291,7 +1425,7 @@ Stage::append(const void* frames, uint64_t n_frames, int mem)
         }
         if (mem == kMemDevice)
             note_consumed(stream_, b);
-        else if (mem != kMemHostPinned)
+        else if (!pitched && mem != kMemHostPinned) // (pitched: stage_host_rows noted it)
             note_consumed(nullptr, b); // copied into staging before return
         done += b;
         if (slab_len_ && (slab_done_ += b) == slab_len_) {
@@ -1459,7 +1593,9 @@ Stage::fused_params(const uint8_t* dsrc, uint32_t n, uint32_t n_fused,
     const StageLevel& L0 = lv_[0];
     FusedParams p{};
     p.src = dsrc;
-    p.src_stride = uint64_t(L0.W) * L0.H * bpp_;
+    // (a pitched device batch read in place: append_frames set its strides)
+    p.src_stride = pitch_row_ ? pitch_frame_ : uint64_t(L0.W) * L0.H * bpp_;
+    p.src_row_stride = uint32_t(pitch_row_ ? pitch_row_ : uint64_t(L0.W) * bpp_);
     p.xy = xy_src_ ? 1u : 0u;
     p.n_frames = n;
     p.n_fused = n_fused;
@@ -1468,7 +1604,12 @@ Stage::fused_params(const uint8_t* dsrc, uint32_t n, uint32_t n_fused,
     p.nbx = parts_along(L0.W, RW);
     p.nby = parts_along(L0.H, 1u << rh_log2);
     // (xy: the acquisition rows, H[0] pixels, are the ones loaded as vectors)
-    p.vec_rows = ((uint64_t(p.xy ? L0.H : L0.W) * bpp_) % 16 == 0 &&
+    // (pitched: the pitch aligns the row starts whatever the row length, and a
+    // ragged last vector stays behind generic_region's nv0 == VEC)
+    p.vec_rows = (((pitch_row_ ? pitch_row_ | pitch_frame_
+                               : uint64_t(p.xy ? L0.H : L0.W) * bpp_) %
+                     16 ==
+                   0) &&
                   reinterpret_cast<uintptr_t>(dsrc) % 16 == 0)
                    ? 1
                    : 0;
@@ -1925,6 +2066,7 @@ Stage::memory_usage() const
         f.pinned += h_stage_[j].n;
     }
     f.device += xbuf_.n;
+    f.device += pack_buf_.n;
     if (arena_.p) { // the rings are views: the arena's pieces beyond them
         uint64_t views = 0;
         for (const StageLevel& L : lv_)

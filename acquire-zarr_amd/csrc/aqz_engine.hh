@@ -33,6 +33,8 @@ hipError_t launch_level(int dtype, int method, const LevelParams& p,
                         hipStream_t stream);
 hipError_t launch_fused_pyramid_3d(int dtype, int method, const FusedParams& p,
                                    hipStream_t stream);
+// aqz_pack.hip: unit = strided::pack_unit of the source and of p.dst
+hipError_t launch_pack_frames(const PackParams& p, uint32_t unit, hipStream_t stream);
 hipError_t launch_transpose_frames(const void* src, void* dst, uint32_t rows,
                                    uint32_t cols, uint32_t n_frames, uint32_t bpp,
                                    hipStream_t stream);
@@ -491,6 +493,18 @@ class Stage
     // back to back, 64 KiB aligned); the stage restarts at frame 0
     void set_ring_offset(uint64_t offset);
     void append(const void* frames, uint64_t n_frames, int mem);
+    // pitched frames (aqz_stage_append_strided; checks and routes in
+    // aqz_strided.hh); contiguous strides are exactly append
+    void append_strided(const void* frames, uint64_t n_frames, int mem, uint64_t row_stride,
+                        uint64_t frame_stride);
+    // device frames of pitched appends by route since creation
+    void source_report(uint64_t* direct, uint64_t* packed) const
+    {
+        if (direct)
+            *direct = direct_frames_;
+        if (packed)
+            *packed = packed_frames_;
+    }
     void synchronize();
     uint64_t frames_written(uint32_t level) const;
     // level-0 frames whose source bytes the stage has finished reading
@@ -585,6 +599,10 @@ class Stage
     };
 
     void run_batch(const uint8_t* dsrc, uint32_t n);
+    void append_frames(const void* frames, uint64_t n_frames, int mem, uint64_t row_stride,
+                       uint64_t frame_stride);
+    void stage_host_rows(int j, const uint8_t* p, uint32_t b, bool pinned, uint64_t row_stride,
+                         uint64_t frame_stride);
     void place_level(StageLevel& L, uint8_t* at = nullptr);
     void place_rings_at(uint64_t offset);
     void calibrate_placement();
@@ -656,6 +674,12 @@ class Stage
     bool xy_src_ = false;    // the batch being launched is in acquisition order
     uint32_t acq_rows_ = 0, acq_cols_ = 0;
     DevBuf xbuf_;
+    // pitched sources (append_strided): the strides of the device batch being
+    // launched (0: contiguous), the packed route's buffer (allocated by the
+    // first packed append) and the frames by route
+    uint64_t pitch_row_ = 0, pitch_frame_ = 0;
+    DevBuf pack_buf_;
+    uint64_t direct_frames_ = 0, packed_frames_ = 0;
     // source consumption: (event, appended frames when it fires)
     std::vector<std::pair<hipEvent_t, uint64_t>> inflight_;
     size_t inflight_head_ = 0;

@@ -557,6 +557,9 @@ generic_region(const FusedParams& p, uint32_t f, uint32_t y0, uint32_t x0,
     const uint32_t npass = 1u << (p.rh_log2 - 4);
     const uint32_t W0 = p.W[0], H0 = p.H[0];
     const T* src = reinterpret_cast<const T*>(p.src + uint64_t(f) * p.src_stride);
+    // pixels from row to row: W0, or a pitched source's row stride (a
+    // multiple of the pixel size; never with xy)
+    const uint64_t RS = p.src_row_stride / sizeof(T);
 
     const Ref r0ref = frame_ref(p, 0, f);
     const bool l1 = p.n_fused >= 1;
@@ -588,9 +591,9 @@ generic_region(const FusedParams& p, uint32_t f, uint32_t y0, uint32_t x0,
                 }
             } else if (p.vec_rows && nv0 == VEC) {
                 const uint4 a = *reinterpret_cast<const uint4*>(
-                  src + uint64_t(y) * W0 + x);
+                  src + uint64_t(y) * RS + x);
                 const uint4 b = *reinterpret_cast<const uint4*>(
-                  src + uint64_t(ya) * W0 + x);
+                  src + uint64_t(ya) * RS + x);
                 __builtin_memcpy(r0, &a, 16);
                 __builtin_memcpy(r1, &b, 16);
             } else {
@@ -598,8 +601,8 @@ generic_region(const FusedParams& p, uint32_t f, uint32_t y0, uint32_t x0,
                 for (int i = 0; i < VEC; ++i) {
                     // right edge replicate: clamp the column
                     const uint32_t xi = min(x + uint32_t(i), W0 - 1);
-                    r0[i] = src[uint64_t(y) * W0 + xi];
-                    r1[i] = src[uint64_t(ya) * W0 + xi];
+                    r0[i] = src[uint64_t(y) * RS + xi];
+                    r1[i] = src[uint64_t(ya) * RS + xi];
                 }
             }
             if (r0ref.tiles) {
@@ -744,13 +747,15 @@ st16(uint8_t* d, const uint4& a)
 }
 
 // The two 16-B row vectors of this thread for one pass of an interior region.
-template<int NTM>
+// PITCH: the rows lie p.src_row_stride bytes apart (a pitched source,
+// aqz_strided.hh), not W[0] * bpp.
+template<int NTM, bool PITCH = false>
 __device__ __forceinline__ void
 load_pass(const FusedParams& p, uint32_t f, uint32_t y0, uint32_t x0,
           uint32_t pass, uint32_t bpp, uint4& a, uint4& b)
 {
     const uint32_t y = y0 + pass * 16 + 2 * (threadIdx.x >> 5);
-    const uint64_t row = uint64_t(p.W[0]) * bpp;
+    const uint64_t row = PITCH ? p.src_row_stride : uint64_t(p.W[0]) * bpp;
     const uint8_t* s = p.src + uint64_t(f) * p.src_stride + uint64_t(y) * row +
                        uint64_t(x0 + (threadIdx.x & 31) * (16 / bpp)) * bpp;
     a = ld16<(NTM & 1) != 0>(s);
@@ -911,7 +916,8 @@ region_xy(const FusedParams& p, uint32_t q, uint32_t& by, uint32_t& bx, bool col
 // cascade invariant live across the row passes, which costs occupancy.
 constexpr uint32_t kPassBatch = 4;
 
-template<typename T, int M, int NTM>
+// PITCH: a pitched source (load_pass).
+template<typename T, int M, int NTM, bool PITCH = false>
 __global__ __launch_bounds__(256) void
 fused_pyramid(const FusedParams p)
 {
@@ -942,7 +948,8 @@ fused_pyramid(const FusedParams p)
         uint4 ra[kPassBatch], rb[kPassBatch];
 #pragma unroll
         for (uint32_t i = 0; i < kPassBatch; ++i) // passes past npass re-read the last
-            load_pass<NTM>(p, f, y0, x0, min(p0 + i, npass - 1), sizeof(T), ra[i], rb[i]);
+            load_pass<NTM, PITCH>(p, f, y0, x0, min(p0 + i, npass - 1), sizeof(T), ra[i],
+                                  rb[i]);
 #pragma unroll
         for (uint32_t i = 0; i < kPassBatch; ++i)
             if (p0 + i < npass)
@@ -1042,7 +1049,10 @@ load_region_xy(const FusedParams& p, uint32_t f, uint32_t y0, uint32_t x0, uint3
 // tile stores, bit 4 level-1/2 stores (the launcher maps p.nt onto one of the
 // instantiated policies).
 // XY: the source is in acquisition order (load_region_xy).
-template<typename T, int M, int NTM, bool XY = false>
+// PITCH: the rows of a frame lie p.src_row_stride bytes apart (a pitched
+// source, aqz_strided.hh; not with XY); every load stays inside its row, as
+// an interior region is 512 bytes of a row at any pitch.
+template<typename T, int M, int NTM, bool XY = false, bool PITCH = false>
 __global__ __launch_bounds__(256) void
 fused_pyramid_strip(const FusedParams p)
 {
@@ -1080,7 +1090,7 @@ fused_pyramid_strip(const FusedParams p)
     if constexpr (XY) {
         load_region_xy<T, NTM>(p, f, y0, x0, ry, cv, ra, rb);
     } else {
-        const uint64_t row = uint64_t(p.W[0]) * sizeof(T);
+        const uint64_t row = PITCH ? p.src_row_stride : uint64_t(p.W[0]) * sizeof(T);
         const uint8_t* s = p.src + uint64_t(f) * p.src_stride + uint64_t(y0 + ry) * row +
                            uint64_t(x0 + cv * VEC) * sizeof(T);
 #pragma unroll
@@ -1810,7 +1820,9 @@ fused_pyramid_strip3d(const FusedParams p)
 // workgroup); it spills even at 4 waves, so XY stages run the single-plane
 // kernel unless knob 65536 asks for this one.
 // ---------------------------------------------------------------------------
-template<typename T, int M, int NTM, bool XY = false, int WPE = 4, int PF = 1>
+// PITCH: a pitched source, as fused_pyramid_strip (not with XY).
+template<typename T, int M, int NTM, bool XY = false, int WPE = 4, int PF = 1,
+         bool PITCH = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE))) void
 fused_pyramid_strip3d_pair(const FusedParams p)
 {
@@ -1845,7 +1857,7 @@ fused_pyramid_strip3d_pair(const FusedParams p)
     const uint32_t G = p.G;
     const uint32_t zm = p.zmask; // bit 1 set (host)
     const uint32_t ry = 16 * w + 2 * hw;
-    const uint64_t row = uint64_t(p.W[0]) * sizeof(T);
+    const uint64_t row = PITCH ? p.src_row_stride : uint64_t(p.W[0]) * sizeof(T);
     const uint8_t* src0 = XY ? p.src
                              : p.src + uint64_t(grp * G + half) * p.src_stride +
                                  uint64_t(y0 + ry) * row + uint64_t(x0 + cv * VEC) * sizeof(T);
@@ -2230,8 +2242,19 @@ launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t stream)
         default: return hipErrorInvalidValue;                                  \
     }
 
+// bytes per pixel of dtype 0..9 (u8 u16 u32 u64 i8 i16 i32 i64 f32 f64)
+constexpr uint32_t kDtypeBytes[10] = { 1, 2, 4, 8, 1, 2, 4, 8, 4, 8 };
+
 // workgroups of the 2-D strip kernel per CU (launch_interior)
 constexpr uint32_t kStripWgPerCu = 6;
+
+// a pitched source (aqz_strided.hh): the interior kernels' PITCH variants,
+// which exist for the shipped tuning only
+static bool
+pitched(const FusedParams& p, size_t bpp)
+{
+    return p.src_row_stride != uint32_t(uint64_t(p.W[0]) * bpp);
+}
 
 // The strip kernel takes 64-row interior regions of <= 4-byte pixels when
 // no level 3-4 output goes to scratch; fused_pyramid takes the rest.
@@ -2251,6 +2274,12 @@ launch_interior(uint32_t blocks, const FusedParams& p, hipStream_t stream)
         }
         if (p.rh_log2 == 6 && !(p.knobs & 128u) &&
             (p.scratch_level == 0 || p.scratch_level >= 5)) {
+            if (pitched(p, sizeof(T))) { // nt == 7, knobs == 0 (launch_fused_pyramid)
+                const uint32_t lds = (163840u / kStripWgPerCu - 512u) & ~255u;
+                hipLaunchKernelGGL((fused_pyramid_strip<T, M, 7, false, true>), dim3(blocks),
+                                   dim3(256), lds, stream, p);
+                return;
+            }
             // Occupancy: at most kStripWgPerCu workgroups per CU, held by
             // unused dynamic LDS (the kernel's registers would allow 8).
             // Same stage A/Bs, round 5 (profiles/r05_occupancy_cap.txt):
@@ -2281,7 +2310,10 @@ launch_interior(uint32_t blocks, const FusedParams& p, hipStream_t stream)
             return;
         }
     }
-    if (p.nt)
+    if (pitched(p, sizeof(T)))
+        hipLaunchKernelGGL((fused_pyramid<T, M, 7, true>), dim3(blocks), dim3(256), 0, stream,
+                           p);
+    else if (p.nt)
         hipLaunchKernelGGL((fused_pyramid<T, M, 7>), dim3(blocks), dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((fused_pyramid<T, M, 0>), dim3(blocks), dim3(256), 0, stream, p);
@@ -2306,6 +2338,12 @@ launch_fused_pyramid(int dtype, int method, const FusedParams& p,
            dtype == 6 || dtype == 8) &&
           p.rh_log2 == 6 &&
           !(p.knobs & 128u) && (p.scratch_level == 0 || p.scratch_level >= 5)))
+        return hipErrorInvalidValue;
+    // a pitched source: no XY load, and interior kernels of the shipped tuning only
+    if (dtype < 0 || dtype > 9)
+        return hipErrorInvalidValue;
+    if (pitched(p, kDtypeBytes[dtype]) &&
+        (p.xy || (interior && (p.nt != 7 || p.knobs != 0))))
         return hipErrorInvalidValue;
     const FusedParams pr = with_xcd_rotation(p, interior);
 #define CALL(T, MM)                                                            \
@@ -2346,11 +2384,18 @@ launch_fused_pyramid_3d(int dtype, int method, const FusedParams& p,
     // acquisition-order planes: only through the strip kernel's XY load
     if (p.xy && !(strip && dtype != 3 && dtype != 7 && dtype != 9))
         return hipErrorInvalidValue;
+    // a pitched source: only the shipped pair kernel has a PITCH variant
+    const bool pitch = dtype >= 0 && dtype <= 9 && pitched(p, kDtypeBytes[dtype]);
+    if (pitch && !(pair && !p.xy && p.nt == 7 && p.knobs == 0))
+        return hipErrorInvalidValue;
     const FusedParams pr = with_xcd_rotation(p, blocks);
 #define CALL(T, MM)                                                            \
     do {                                                                       \
         const dim3 gd{ uint32_t(blocks), 1, 1 };                              \
-        if (p.xy && pair && p.nt)                                             \
+        if (pitch)                                                            \
+            hipLaunchKernelGGL((fused_pyramid_strip3d_pair<T, MM, 7, false, 4, 1, true>), gd, \
+                               dim3(512), 0, stream, pr);                      \
+        else if (p.xy && pair && p.nt)                                        \
             hipLaunchKernelGGL((fused_pyramid_strip3d_pair<T, MM, 7, true>), gd, dim3(512), \
                                0, stream, pr);                                 \
         else if (p.xy && p.nt)                                                \

@@ -101,6 +101,23 @@ struct FusedParams
     uint64_t bpc;            // bytes per chunk
     FastDiv d_nreg_in, d_nbx_in;
     uint32_t W[kMaxFused + 1], H[kMaxFused + 1], ntx[kMaxFused + 1];
+    // bytes between rows of a level-0 frame (W[0] * bpp unless the source is
+    // pitched, aqz_strided.hh; never with xy).  Last and 32 bits wide: it
+    // fills the struct's tail padding, so the fields above, the struct's size
+    // and with it the hidden kernel arguments behind it keep their offsets.
+    uint32_t src_row_stride;
+};
+static_assert(sizeof(FusedParams) == 456, "FusedParams must not grow: the kernels' "
+                                          "argument offsets are part of their code");
+
+// pack_frames (aqz_pack.hip): row y of frame k, row_bytes long, from src +
+// k * frame_stride + y * row_stride to dst + (k * rows + y) * row_bytes.
+struct PackParams
+{
+    const uint8_t* src;
+    uint8_t* dst;
+    uint64_t row_stride, frame_stride, row_bytes;
+    uint32_t rows, n_frames;
 };
 
 // One output frame (or partial plane) of the generic level kernel.  Pixel

@@ -312,7 +312,9 @@ aqz_status aqz_stage_set_stream(aqz_stage* st, void* stream);
  * (a hipStream_t): append device frames produced there without a host
  * synchronisation (e.g. a torch stream that filled them). */
 aqz_status aqz_stage_wait_stream(aqz_stage* st, void* stream);
-/* Append n_frames full level-0 frames (contiguous, frame after frame).
+/* Append n_frames full level-0 frames (contiguous, frame after frame; pitched
+ * rows, sub-rectangles of a larger canvas and strided views go to
+ * aqz_stage_append_strided, below, without a packing copy).
  * Equivalent to n_frames calls of MultiscaleArray::write_frame.
  *  - AQZ_MEM_HOST: copied into a pinned staging buffer by a few host threads
  *    before return, so the caller may reuse it at once, as with
@@ -331,6 +333,43 @@ aqz_status aqz_stage_wait_stream(aqz_stage* st, void* stream);
  * Host sources are staged into 16-byte-aligned device buffers. */
 aqz_status aqz_stage_append(aqz_stage* st, const void* frames,
                             uint64_t n_frames, int32_t mem);
+/* aqz_stage_append for pitched frames: `frames` points at pixel (0, 0) of the
+ * first frame, and row y of frame k starts at frames + k * frame_stride +
+ * y * row_stride (bytes).  Each row holds W * bpp bytes; W and H are those of
+ * the frames as appended (for an XY-swapped storage order: the acquisition
+ * rows).  Covers a frame grabber's line pitch, a sub-rectangle of a larger
+ * sensor frame and a strided view of a tensor.
+ * Contract: only bytes of pixels inside these rectangles are ever read.  The
+ * bytes between rows may belong to someone else, and the last rectangle may
+ * end at the end of an allocation.
+ * The result is defined as the chunk layers and has_data flags that
+ * aqz_stage_append gives for the same pixels packed contiguously.  Every
+ * memory kind works; lifetime and aqz_stage_frames_consumed are those of
+ * aqz_stage_append (a pinned source whose pitch the runtime's 2-D copy
+ * refuses is staged like a pageable one and consumed on return); bounds
+ * (status 12), z slabs, first_frame and batching too.  Strides of W * bpp and
+ * W * H * bpp are exactly aqz_stage_append.
+ * AQZ_STATUS_INVALID_ARGUMENT with an aqz_last_error text, nothing enqueued
+ * and frames_written unchanged: row_stride < W * bpp; frame_stride <
+ * (H - 1) * row_stride + W * bpp; either stride or the address no multiple of
+ * the pixel size; n_frames * frame_stride overflowing 64 bits; a stage
+ * created with level0_split_on_host (its host split takes contiguous host
+ * frames).
+ * Routes.  Host sources are packed on their way into the stage's contiguous
+ * staging buffers (pageable: by the host threads' row copy; pinned: by a 2-D
+ * DMA) and run no extra kernel.  A device source whose address, row_stride
+ * and frame_stride are multiples of 16 is read in place by the fused kernels
+ * (2-D stages; on a 2x2x2 stage the whole z groups of a batch that the pair
+ * kernel takes) when the storage order is not XY-swapped.  Any other device
+ * source -- a misaligned pitch, XY storage orders, the frames of a 2x2x2
+ * batch that go to the generic cascade, non-default bench tuning -- is first
+ * packed by a copy kernel into a stage-owned buffer of max_batch_frames
+ * frames.  That buffer is allocated by the first packed append;
+ * aqz_stage_memory_usage reports it from then on, and it is outside
+ * aqz_stage_estimate_memory, like the verify decoder's state.
+ * aqz_stage_source_report (aqz_gpu_bench.h) counts the frames by route. */
+aqz_status aqz_stage_append_strided(aqz_stage* st, const void* frames, uint64_t n_frames,
+                                    int32_t mem, uint64_t row_stride, uint64_t frame_stride);
 aqz_status aqz_stage_synchronize(aqz_stage* st);
 /* frames written so far to `level` (Array::frames_written_) */
 uint64_t aqz_stage_frames_written(const aqz_stage* st, uint32_t level);

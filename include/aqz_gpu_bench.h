@@ -147,6 +147,13 @@ aqz_status aqz_stage_timing_mark(aqz_stage* st, int32_t which);
 aqz_status aqz_stage_timing_elapsed(aqz_stage* st, double* ms);
 /* Name of the dominant kernel symbol (for matching rocprof output). */
 const char* aqz_stage_dominant_kernel(const aqz_stage* st);
+/* Device frames of aqz_stage_append_strided by route since creation:
+ * direct_frames were read in place by the fused kernels, packed_frames went
+ * through the packing kernel first.  Contiguous frames (aqz_stage_append, or
+ * contiguous strides) and host-staged frames count in neither.  Either
+ * pointer may be NULL. */
+aqz_status aqz_stage_source_report(const aqz_stage* st, uint64_t* direct_frames,
+                                   uint64_t* packed_frames);
 /* Ranges the device zstd far pass walked each segment of `level`'s last
  * compressed layer in (1 = one sequential walk; 0 = no far pass or no
  * compression yet): the ranges follow from the layer geometry alone. */
